@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Permutect artifact-model hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a process group in the environment: bench.py starts `python -m torch.distributed.run` with N ranks itself
 (before anything touches a GPU) and relays rank 0's line; the driver's own torchrun launch works as before.
@@ -9,12 +9,27 @@ N > 1 without a process group in the environment: bench.py starts `python -m tor
 Metric (BASELINE.json): read-sets/sec, "train fwd+bwd; filter fwd".  The headline `value` is BASELINE.json configs[1]:
 train_model on synthetic WGS-shaped ReadSet batches with the production-shaped hyperparameters P0 (59 845 parameters):
 one "step" = forward + losses + backward + (DP: bucketed RCCL gradient all-reduce, the big bucket under the rest of the
-backward) + global-norm clip + AdamW on one prepared batch already resident in HBM.  The SAME run then times the
-filter_variants forward (configs[2]) over the same resident batches and prints it as `"filter": {...}` inside the line.
+backward) + global-norm clip + AdamW on one prepared batch already resident in HBM.
+
+A plain run does only what the headline needs: it builds the resident batches, warms up, times exactly K steps and prints
+the line (with `roofline`, timed inside those K steps).  `--full` adds everything else below: the filter_variants forward
+(configs[2]) over the same resident batches as `"filter": {...}`, the other sizes, depths and configurations, the parity
+check against the CPU oracle and the CPU baseline (`--no-extras` / `--no-cpu-baseline` still leave parts of it out).
+
+`--dump-outputs DIR`: after the timed steps, what the headline path computed in its LAST timed step, as DIR/<name>.npy
+(float32): compute_batch_output's logits_b, logits_bk, features_be, ref_features_be and, for the training step, the
+per-variant losses, total_loss and the flat parameters and gradients after the step; the rows of a packed resident batch
+back in the order of its synthetic arrays.  The batches and the initial weights are seeded, and the last timed training step
+starts from those weights and a fresh optimizer state (restored in front of it, inside the timed region -- three device copies
+of the flat parameter and moment buffers, so the ms_per_step of a dumping run is not quite a plain run's: the backward's float
+atomics differ in their last bits from run to run, and a few hundred AdamW steps make different parameters of that), so that
+two builds can be compared output for output.  Above 64 MB in all, the per-variant arrays hold a fixed, seeded sample of the rows, whose
+numbers are in sample_rows.npy.
 
 ONE JSON line on rank 0 carries, besides the contract's keys:
   roofline      dominant kernel (pmt_backward_kernel), HIP-event timed inside the timed region; `traffic` only from a
                 profiles/*.json whose recorded hash of the kernel sources equals this tree's
+and with --full:
   filter        the filter-forward half of the metric: value, ms_per_step, its own roofline (pmt_forward_kernel)
   small_batch   the reference's default batch sizes (training 64, inference 8192: parameters.py:214,236-242) and twice the
                 headline's batch (131072), N = 1 only
@@ -171,6 +186,44 @@ def algorithmic_macs_per_read(model, padded=False):
     return macs
 
 
+DUMP_BUDGET_BYTES = 63 * 10**6  # (at most 64 MB written, the .npy headers included)
+
+
+def dump_outputs(directory, mode, batch, result, eng):
+    """--dump-outputs: what the last timed step of `mode` returned to its caller (`result`: train_step's (output, losses) or
+    filter_step's output) and, for a training step, the flat parameters and gradients it left, as DIR/<name>.npy in float32.
+    Per-variant rows go back to the order of the arrays the batch was built from (Batch.order of a packed batch)."""
+    out, losses = result if mode == "train" else (result, None)
+    rows = {"logits_b": out.logits_b, "logits_bk": out.logits_bk, "features_be": out.features_be, "ref_features_be": out.ref_features_be}
+    whole = {}
+    if losses is not None:
+        rows.update(supervised_losses_b=losses.supervised_losses_b, unsupervised_losses_b=losses.unsupervised_losses_b,
+                    alt_count_losses_b=losses.alt_count_losses_b, source_prediction_losses_b=losses.source_prediction_losses_b,
+                    total_losses_b=losses.total_losses_b)
+        whole.update(total_loss=losses.total_loss, params=eng.space.theta, grads=eng.space.gtheta)
+    rows = {k: v.detach().float().cpu().numpy() for k, v in rows.items() if v is not None}
+    whole = {k: v.detach().float().cpu().numpy() for k, v in whole.items()}
+    n = batch.size()
+    order = getattr(batch, "order", None)
+    if order is not None:
+        order = np.asarray(order, dtype=np.int64)
+        for k, a in rows.items():
+            host = np.empty_like(a)
+            host[order] = a
+            rows[k] = host
+    per_row = sum(a.nbytes for a in rows.values()) // n
+    fixed = sum(a.nbytes for a in whole.values())
+    if fixed + per_row * n > DUMP_BUDGET_BYTES:  # a fixed, seeded sample of the rows (and their numbers, as float64)
+        keep = max(1, (DUMP_BUDGET_BYTES - fixed) // (per_row + 8))
+        sample = np.sort(np.random.default_rng(0).choice(n, size=min(n, keep), replace=False))
+        rows = {k: a[sample] for k, a in rows.items()}
+        whole["sample_rows"] = sample.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in {**rows, **whole}.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted({**rows, **whole})
+
+
 # ---- the CPU baseline ---------------------------------------------------------------------------------------------------
 def _oracle_problem(b):
     from oracle import artifact_oracle as O  # checker / baseline only -- never the product path
@@ -296,8 +349,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)  # ~1 s of train steps, ~0.2 s of filter forwards
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the filter forward, the other sizes / depths / configurations, the parity check against "
+                         "the CPU oracle and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline path computed in its last timed step to DIR/<name>.npy (float32, at most 64 MB).  "
+                         "Training: that step starts from the seeded weights and a fresh optimizer state, restored by three small "
+                         "device copies INSIDE the timed region -- compare ms_per_step with runs that dump too")
     ap.add_argument("--mode", choices=["both", "train", "filter"], default="both",
-                    help="both: the headline is the train step and the filter forward is timed in the same run (\"filter\" key); "
+                    help="both: the headline is the train step; with --full the filter forward is timed in the same run (\"filter\" key); "
                          "train / filter: only that half (filter: the headline keys describe the filter forward)")
     ap.add_argument("--batch", type=int, default=65536, help="read sets per step per GPU")
     ap.add_argument("--resident-batches", type=int, default=4, help="distinct synthetic batches kept in HBM per GPU")
@@ -311,8 +371,8 @@ def main():
     ap.add_argument("--strict-parity", action="store_true",
                     help="fail on ANY variant beyond 1e-4 of the fp32 oracle; default: such a variant is recomputed in fp64 and the run fails "
                          "unless the excess is the fp32 reference's own rounding (counted and reported in parity_check either way)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the small-batch points and the oracle parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the small-batch points and the oracle parity check")
     ap.add_argument("--rehearse", action="store_true",
                     help="development only: run the N > 1 code path on a box with fewer GPUs than ranks (ranks share the "
                          "cards, gloo instead of RCCL); the numbers mean nothing")
@@ -323,6 +383,7 @@ def main():
     ap.add_argument("--dataset-variants", type=int, default=1 << 20, help="--data loader: variants in the synthetic dataset")
     ap.add_argument("--chunk-variants", type=int, default=1 << 18, help="--data loader: variants per HBM-resident chunk")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras  # (every leg beyond the headline and the filter forward)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)  # does not return
@@ -413,10 +474,13 @@ def main():
     prerolled = {}
     preroll_s = args.preroll
 
-    def timed(mode, pool, steps, warmup):
+    def timed(mode, pool, steps, warmup, keep=None):
         """W untimed + exactly K timed steps between barrier + synchronize brackets; max over ranks.  Returns (seconds,
         kernel milliseconds, per-step milliseconds): the last from one HIP event behind every step -- no synchronisation
-        inside the loop -- so that the spread of the steps is visible next to their mean."""
+        inside the loop -- so that the spread of the steps is visible next to their mean.  `keep` (a dict): keep[mode] =
+        (batch, what the step returned) of the last timed step, which then starts from the parameters and optimizer state timed() was
+        entered with: the float atomics of the backward make every step's gradient differ in its last bits from run to run, and a few
+        hundred AdamW steps turn that into different parameters, so only a step from a known state can be compared between runs."""
         model.train(mode == "train")
         fn = train_step if mode == "train" else filter_step
         nxt = (lambda i: pool[i % len(pool)]) if stream_batches is None or pool is not batches else (lambda i: next(stream_batches))
@@ -424,6 +488,7 @@ def main():
         # `--steps 20` run would sit inside that ramp; resident batches only (a streamed pass has its own fill)
         t_pre = time.perf_counter()
         did_preroll = preroll_s > 0 and pool is batches and stream_batches is None
+        snap = (eng.space.theta.clone(), opt.state_dict()) if mode == "train" and keep is not None else None
         if did_preroll:
             go = True
             while go:
@@ -448,8 +513,16 @@ def main():
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(steps):
-            fn(nxt(warmup + i))
+            if snap is not None and i + 1 == steps:  # (device copies and host bookkeeping only: no synchronisation)
+                with torch.no_grad():
+                    eng.space.theta.copy_(snap[0])
+                opt.load_state_dict(snap[1])
+                eng.params_changed()
+            b = nxt(warmup + i)
+            res = fn(b)
             marks[i + 1].record()
+            if keep is None or i + 1 < steps:  # (released at once: the next step allocates into the same memory)
+                b = res = None
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -462,6 +535,8 @@ def main():
         kernel_ms["_samples"] = {k: len(v) for k, v in eng.timers.items()}
         eng.timers, eng.timer_stride = None, 1
         per_step = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(steps)])
+        if keep is not None:
+            keep[mode] = (b, res)
         return elapsed, kernel_ms, per_step
 
     def step_stats(elapsed, per_step):
@@ -500,8 +575,16 @@ def main():
                 "pmc_source": pmc.get("source")}
 
     results = {}
+    last_step = {} if args.dump_outputs else None  # (every rank: the dumped step starts from the same state on all of them)
+
+    def dump(mode):
+        if last_step is not None and rank == 0:  # (right after the timed region: nothing has moved the parameters since its last step)
+            names = dump_outputs(args.dump_outputs, mode, *last_step.pop(mode), eng)
+            note(f"{mode}: the last timed step's outputs written to {args.dump_outputs}: {', '.join(names)}")
+
     if args.mode in ("both", "train"):
-        elapsed, kms, per_step = timed("train", batches, args.steps, args.warmup)
+        elapsed, kms, per_step = timed("train", batches, args.steps, args.warmup, keep=last_step)
+        dump("train")
         r = roofline("pmt_backward_kernel", 2.0 * fwd_flops, kms["pmt_backward"])  # dgrad + wgrad; in-kernel recompute not counted
         r["matrix_pipe"] = ("fp32 accumulation on the 16-bit matrix pipes.  Forward (both kernels): fp32-equivalent, three f16 MFMAs on two-piece "
                             "splits of both operands with the low piece scaled by 2^12 (23 significant bits per operand; six bf16 MFMAs on "
@@ -516,10 +599,12 @@ def main():
         r["kernel_timing"] = f"HIP events on the launch stream around {kms['_samples']['pmt_backward']} of the {args.steps} launches inside the timed region"
         results["train"] = (elapsed, r, step_stats(elapsed, per_step))
         note(f"train: {1e3 * elapsed / args.steps:.3f} ms/step over {elapsed:.3f} s (steps {per_step.min():.3f} .. {per_step.max():.3f} ms), kernels {kms}")
-    if args.mode in ("both", "filter"):
+    if args.mode == "filter" or (args.mode == "both" and args.full):
         if stream_batches is not None:
             loader_shuffle[0] = False
-        elapsed, kms, per_step = timed("filter", batches, args.steps, args.warmup)
+        elapsed, kms, per_step = timed("filter", batches, args.steps, args.warmup, keep=last_step if args.mode == "filter" else None)
+        if args.mode == "filter":
+            dump("filter")
         rf_ = roofline("pmt_forward_kernel", fwd_flops, kms["pmt_forward"])
         rf_["kernel_timing"] = f"HIP events on the launch stream around {kms['_samples']['pmt_forward']} of the {args.steps} launches inside the timed region"
         results["filter"] = (elapsed, rf_, step_stats(elapsed, per_step))
@@ -527,7 +612,7 @@ def main():
 
     # ---- the reference's default batch sizes beside the build's best: N = 1, resident batches only ------------
     small = None
-    if world == 1 and not args.no_extras and args.data == "resident" and args.depth == "wgs":
+    if world == 1 and extras and args.data == "resident" and args.depth == "wgs":
         small = {}
         for bsz, k in ((64, 200), (8192, 40), (131072, 10)):  # (the last: twice the headline's batch)
             pool = []
@@ -561,7 +646,7 @@ def main():
 
     # ---- BASELINE configs[4]: high-depth stress, mean 600 reads per variant (read sets split over workgroups: layered launches) --
     stress = None
-    if world == 1 and not args.no_extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
+    if world == 1 and extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
         sb = 1420  # the same ~852 K reads per step as the WGS headline batch
         pool, sreads = [], 0
         srng = np.random.default_rng(4040)
@@ -602,7 +687,7 @@ def main():
     # ---- the same training step with the reference's --dropout_p (mlp.py:57-58): the masks are generated in the kernels, such a
     #      step runs the generic instances ("Dropout") ---------------------------------------------------------
     dropout = None
-    if world == 1 and not args.no_extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
+    if world == 1 and extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
         dparams = p0_params()
         dparams.dropout_p = 0.25
         dmodel = ArtifactModel(dparams, device=dev, **P0_DIMS)
@@ -633,7 +718,7 @@ def main():
 
     # ---- BASELINE configs[1] / [2] as DATASETS: batches streamed from host memory through the device chunk loader -------------
     loader = None
-    if world == 1 and not args.no_extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
+    if world == 1 and extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
         from permutect_amd.data.memory_mapped_data import MemoryMappedData
         from permutect_amd.data.reads_dataset import ReadsDataset
         from permutect_amd.tools.posterior_data import make_posterior_mmap
@@ -747,7 +832,7 @@ def main():
     # ---- N > 1: filter_variants as it is split over GPUs -- the candidates of ONE dataset in N contiguous shards, a rank each,
     #      no collective on the data path, the shards' posterior rows concatenated on rank 0 (tools/posterior_data.make_posterior_mmap) ----
     sharded_filter = None
-    if world > 1 and not args.no_extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
+    if world > 1 and extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both":
         try:
             from permutect_amd.data.memory_mapped_data import MemoryMappedData
             from permutect_amd.data.reads_dataset import ReadsDataset
@@ -779,7 +864,7 @@ def main():
     # ---- a model that is NOT the production shape: the reference's test configuration T0 on its own kernel instances (engine/
     #      instances.py: the library built around its tile counts) against the generic instance every such model used to run ---------
     shapes = None
-    if world == 1 and not args.no_extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both" and args.dtype == "f32":
+    if world == 1 and extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both" and args.dtype == "f32":
         from permutect_amd.parameters import t0_params, wide_params
         shapes = {}
         for label, env in (("instance", None), ("generic", "any"), ("wide_instance", None), ("wide_generic", "any")):
@@ -839,7 +924,7 @@ def main():
     # ---- the same training step on the build whose backward runs six-MFMA (fp32-equivalent) products: what the 16-bit operands buy ----
     six = None
     alt6 = os.path.join(ROOT, "permutect_amd", "libpermutect_amd_alt6.so")
-    if (world == 1 and rank == 0 and not args.no_extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both"
+    if (world == 1 and rank == 0 and extras and args.data == "resident" and args.depth == "wgs" and args.mode == "both"
             and args.dtype == "f32" and os.path.exists(alt6) and "PMT_LIB" not in os.environ):
         torch.cuda.synchronize()
         res = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", "train", "--steps", "100", "--warmup", "20", "--no-extras",
@@ -854,7 +939,7 @@ def main():
 
     # ---- parity of what was just timed: EVERY variant of resident batch 0 (one whole launch) against the CPU oracle ------------
     parity = None
-    if rank == 0 and not args.no_extras and first_host is not None and args.depth == "wgs" and batches:
+    if rank == 0 and extras and first_host is not None and args.depth == "wgs" and batches:
         from oracle import artifact_oracle as O  # the checker, never the product path
         from tests.helpers import config_for
         ints, floats, packed = first_host
@@ -951,7 +1036,7 @@ def main():
             sweep = committed_parity_sweep()
             if sweep is not None:
                 line["parity_sweep"] = sweep
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist is not None:

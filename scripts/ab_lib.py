@@ -10,7 +10,7 @@ for rep in range(2):
         env = dict(os.environ)
         if lib != "default":
             env["PMT_LIB"] = os.path.abspath(lib)
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-extras", "--no-cpu-baseline", "--steps", "100", "--warmup", "10"],
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--steps", "100", "--warmup", "10"],
                              env=env, capture_output=True, text=True)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         if not line:

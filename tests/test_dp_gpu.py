@@ -80,7 +80,7 @@ def test_bench_two_rank_path(extra):
     share this box's one card (--rehearse: gloo instead of RCCL, the numbers mean nothing), spawned the way `--gpus N` spawns them.
     The line must say two ranks took part, count both ranks' read sets, and show that the overlap hook fired once per step."""
     batch = "128" if "stress" in extra else "4096"
-    flags = ["--gpus", "2", "--rehearse", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+    flags = ["--gpus", "2", "--rehearse", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"]
     if "--batch" not in extra:
         flags += ["--batch", batch]
     line = _bench_line(*flags, *extra)
@@ -97,7 +97,7 @@ def test_bench_two_rank_path(extra):
 def test_bench_two_rank_sharded_filter_pass():
     """bench.py's N > 1 line also carries the filter as it is split over GPUs: one dataset, a contiguous shard per rank, the posterior
     rows concatenated on rank 0 (`filter_sharded_dataset`)."""
-    line = _bench_line("--gpus", "2", "--rehearse", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--batch", "4096")
+    line = _bench_line("--gpus", "2", "--rehearse", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--batch", "4096")
     f = line["filter_sharded_dataset"]
     assert line["n_gpus"] == 2 and f["rows_on_rank0"] == f["candidates"] > 0 and f["value"] > 0
 
