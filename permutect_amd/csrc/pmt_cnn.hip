@@ -434,8 +434,9 @@ extern "C" int pmt_cnn_forward(const PmtModel* model_host, const PmtModel* model
                                float* stash, void* stream) {
     const int rc = cnn_check(model_host);
     if (rc) return rc;
-    if (!model_dev || !theta || !packed || !haplotypes || !out || n < 0) return PMT_E_INVALID;
-    if (n == 0) return PMT_OK;
+    if (n < 0) return PMT_E_INVALID;
+    if (n == 0) return PMT_OK;  // (before the pointers: an empty batch's tensors have none)
+    if (!model_dev || !theta || !packed || !haplotypes || !out) return PMT_E_INVALID;
     {   // the batched-column kernels where they cover the model (with `stash`: in the layout their backward reads)
         const int rc3 = pmt_cnn3_try_forward(model_host, theta, haplotypes, hap_stride, n, out, out_stride, stash, stream);
         if (rc3 <= 0) return rc3;
@@ -473,8 +474,9 @@ extern "C" int pmt_cnn_backward(const PmtModel* model_host, const PmtModel* mode
                                 void* stream) {
     const int rc = cnn_check(model_host);
     if (rc) return rc;
-    if (!model_dev || !theta || !packed || !haplotypes || !d_out || !grad_theta || n < 0) return PMT_E_INVALID;
+    if (n < 0) return PMT_E_INVALID;
     if (n == 0) return PMT_OK;
+    if (!model_dev || !theta || !packed || !haplotypes || !d_out || !grad_theta) return PMT_E_INVALID;
     {
         const int rc3 = pmt_cnn3_try_backward(model_host, theta, haplotypes, hap_stride, n, d_out, d_out_stride, stash, grad_theta, workspace,
                                                   workspace_floats, stream);

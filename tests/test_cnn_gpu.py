@@ -21,7 +21,11 @@ from tests.test_forward_gpu import check_outputs
 pytestmark = pytest.mark.gpu
 
 # which family runs which stack.  wave: at most two convolutions of at most 32 output channels (or ONE of at most 64 with <= 32 im2col columns), im2col columns <= 96 wide;
-# batched: exactly conv k3 -> pool 2 -> act -> conv k3 -> act -> flatten -> linear on 21 positions (P0_CNN); general: everything.
+# batched: exactly conv k3 -> pool 2 -> act -> conv k3 -> act -> flatten -> linear with leaky_relu or selu in the two activation slots, on 21 or 20
+# positions (7 behind the second convolution); general: everything.  The fixtures here reach, of the compiled instances: batched
+# `cnn3_forward_bf<.., 21, LEAKY, LEAKY, true | false>` / `cnn3_forward<.., 21>` (batched_fp32), `cnn3_backward`; wave `cnn2_forward<2>` + `cnn2_backward<2, 2, 6>` (p0_b16) and
+# `cnn2_forward<4>` + `cnn2_backward<4, 2, 1>` (t0_b8); the general pair.  The rest -- the generic-length / generic-activation batched forwards,
+# `cnn3_fold`, `cnn2_backward<2, 6, 6>` -- and every instance at its scheduling edges: tests/test_cnn_instances_gpu.py (ROWS).
 ACCEPTS = {
     "p0_cnn_legacy": {"auto", "general"},
     "t0_cnn_options": {"auto", "general"},

@@ -423,6 +423,54 @@ def test_no_mfma_accumulates_onto_another_opcodes_result_without_wait_states():
     assert found == [], found[:5]
 
 
+def test_every_cnn_kernel_instance_is_claimed_by_a_test_row():
+    """tests/test_cnn_instances_gpu.py runs every compiled instance of the haplotype-CNN kernels at the edges of its scheduling rule; its
+    table says which row reaches which kernel symbol.  Here the table is held against the build: the demangled `pmt_cnn*_kernel` symbols
+    of the gfx950 code objects in every library the build made.  The default library's set must EQUAL the table's (an instance added
+    without a test row fails here, and so does a row that claims a symbol nobody compiled); the other libraries (wide builds, per-shape
+    instances) may carry no CNN kernel the table does not know."""
+    import glob
+    import importlib.util
+    import subprocess
+    import tempfile
+    from tests.test_cnn_instances_gpu import ROWS, claimed_kernels, kernel_name
+    spec = importlib.util.spec_from_file_location("check_mfma_chains", os.path.join(ROOT, "scripts", "check_mfma_chains.py"))
+    chk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(chk)
+
+    def cnn_kernels(path):
+        found = set()
+        with tempfile.TemporaryDirectory() as tmp:
+            objects = chk.code_objects(path, tmp)
+            assert objects, path
+            for co in objects:
+                table = subprocess.run([chk.LLVM + "llvm-readelf", "--symbols", "--wide", "--demangle", co], capture_output=True, text=True, check=True).stdout
+                for line in table.splitlines():
+                    cols = line.split(None, 7)  # Num Value Size Type Bind Vis Ndx Name
+                    if len(cols) == 8 and cols[3] == "FUNC" and re.search(r"\bpmt_cnn\d*_\w+_kernel\b", cols[7]):
+                        found.add(kernel_name(cols[7]))
+        return found
+
+    assert kernel_name("void pmt_cnn2_forward_kernel<2>(PmtModel const*, float const*)") == "pmt_cnn2_forward_kernel<2>"
+    assert kernel_name("pmt_cnn_forward_kernel.kd") == "pmt_cnn_forward_kernel"
+    claimed = claimed_kernels()
+    assert all(row.kernels or row.refuses == "forward" for row in ROWS)  # a row without kernels is a refusal
+    default = cnn_kernels(os.path.join(ROOT, "permutect_amd", "libpermutect_amd.so"))
+    assert len(default) >= 14, sorted(default)
+    assert default - claimed == set(), f"compiled, but no row of tests/test_cnn_instances_gpu.py runs it: {sorted(default - claimed)}"
+    assert claimed - default == set(), f"claimed by a row, but not in the library: {sorted(claimed - default)}"
+    others = sorted(set(glob.glob(os.path.join(ROOT, "permutect_amd", "*.so")) + glob.glob(os.path.join(ROOT, "permutect_amd", "instances", "*.so")))
+                    - {os.path.join(ROOT, "permutect_amd", "libpermutect_amd.so")})
+    assert len(others) >= 4, others
+    for path in others:
+        extra = cnn_kernels(path) - claimed
+        assert extra == set(), (path, sorted(extra))
+    # the kernel trace of one run of the table on the GPU (rocprofv3 --kernel-trace --stats): the same set
+    with open(os.path.join(ROOT, "profiles", "cnn_instances_kernel_names.txt")) as f:
+        traced = {kernel_name(line) for line in f if line.strip() and not line.startswith("#")}
+    assert traced == claimed, (sorted(traced - claimed), sorted(claimed - traced))
+
+
 def test_instance_libraries_carry_the_default_librarys_build_id(tmp_path, monkeypatch):
     """a per-shape library kept from an earlier state of the tree must not be reused.  Every build of the library carries a hash
     of the sources (pmt_build_id); engine/instances.py reads it out of the FILE (a library it has mapped cannot be replaced by a rebuilt
