@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PMT_ABI_VERSION 10
+#define PMT_ABI_VERSION 11
 
 /* bits of the fault word (PmtBatch.join_fault) */
 #define PMT_FAULT_JOIN 1
@@ -382,6 +382,24 @@ int pmt_downsample_counts(const PmtDownsample* args, float* ref_fracs, float* al
  * ascending order, all kept ref rows of all variants then all kept alt rows, like the reference's read_indices. */
 int pmt_downsample_index(const PmtDownsample* args, const float* ref_fracs, const float* alt_fracs,
                          const int32_t* new_ref_offsets, const int32_t* new_alt_offsets, int64_t* read_index, void* stream);
+
+/* The one-off fit of the downsampler's mixture weights before training (reference training/downsampler.py:125-158,
+ * `optimize_downsampling_balance`: AdamW steps through torch on tensors of a few thousand floats) as ONE persistent launch: a
+ * wavefront per (source, label, variant type) cell -- the loss is a sum over cells and AdamW is element-wise, so the 15 S cells are
+ * independent problems of 160 unknowns -- runs all `steps` iterations with its logits, moments, counts and the two transition tables
+ * in registers; global memory is read at the start and written at the end.  No atomics and nothing between workgroups: run-to-run
+ * bit-identical.  Plain fp32; the loss and gradient are those of the torch fit (permutect_amd/training/downsampler.py), the AdamW is
+ * torch.optim.AdamW's (fresh moments, bias corrections from the step number in double precision).
+ *   counts_slvra [S][3][5][4][5]; ref_trans_kry [4][4][4], alt_trans_haz [4][5][5]: the module's binned transition tables;
+ *   ref_logits_slvrak / alt_logits_slvrah [S][3][5][4][5][4]: the `.original` tensors, starting point in, fitted logits out;
+ *   loss_before_after (optional) [15 S][2]: per cell the loss at the starting point and after the last step (0 for a cell without data,
+ *   whose logits -- like those of an entry with a zero count -- see the weight decay only).
+ * steps == 0 writes the losses only.  steps < 0 or > PMT_FIT_MAX_STEPS, num_sources < 1 or a NULL table / logits / counts:
+ * PMT_E_INVALID, nothing launched. */
+#define PMT_FIT_MAX_STEPS 200000    /* the reference runs 10 000; a launch is `steps` dependent iterations of a few microseconds */
+int pmt_downsample_fit(const float* counts_slvra, int32_t num_sources, const float* ref_trans_kry, const float* alt_trans_haz,
+                       float* ref_logits_slvrak, float* alt_logits_slvrah, int32_t steps, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, float* loss_before_after, void* stream);
 
 /* Per-variant losses (reference architecture/artifact_model.py:267-325). */
 typedef struct PmtLossArgs {

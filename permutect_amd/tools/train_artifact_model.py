@@ -9,6 +9,7 @@ the plots are out of scope: `--tensorboard_dir` is accepted a
 from __future__ import annotations
 
 import argparse
+import time
 
 import torch
 
@@ -35,18 +36,30 @@ def main_without_parsing(args, log=print):
     dist, rank, world, device = init_from_env()  # before anything else touches the GPU
     log = log if rank == 0 else (lambda *a, **k: None)
     pretrained = getattr(args, constants.PRETRAINED_ARTIFACT_MODEL_NAME, None)
+    clock = [time.perf_counter()]
+
+    def stage(name):  # wall seconds of the stage that just ended (the downsampler fit's own line comes from train_artifact_model)
+        now = time.perf_counter()
+        log(f"stage {name}: {now - clock[0]:.2f} s")
+        clock[0] = now
+
     data = MemoryMappedData.load_from_tarfile(getattr(args, constants.TRAIN_TAR_NAME))
+    stage("tar load")
     train_dataset = ReadsDataset(data, num_folds=NUM_FOLDS, folds_to_use=all_but_last_fold(NUM_FOLDS))
     valid_dataset = ReadsDataset(data, num_folds=NUM_FOLDS, folds_to_use=last_fold_only(NUM_FOLDS))
+    stage("fold split")
     if pretrained is not None:
         model, _, _ = load_model(pretrained, device=device)
     else:
         model = ArtifactModel(params=params, num_read_features=train_dataset.num_read_features(),
                               num_info_features=train_dataset.num_info_features(), haplotypes_length=train_dataset.haplotypes_length(),
                               device=device)
-    history = train_artifact_model(model, train_dataset, valid_dataset, training_params, dist=dist, log=log)
+    stage("model load" if pretrained is not None else "model build")
+    history = train_artifact_model(model, train_dataset, valid_dataset, training_params, dist=dist, log=log, timing_log=log)
+    stage("training (downsampler fit + epochs, each with a line of its own above)")
     if rank == 0:
         model.save_model(path=getattr(args, constants.OUTPUT_NAME))
+        stage("save")
     if dist is not None:
         dist.barrier()  # (nobody leaves -- and tears the process group down -- while rank 0 still writes)
     return history

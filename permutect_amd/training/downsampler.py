@@ -11,6 +11,8 @@ bins; deterministic, pinned by tests/golden/downsampler_fit.npz).  Module layout
 (`parametrizations.log_ref_weights_slvrak.original`, ..., `beta_basis`, `binned_ref_trans_kry`, `binned_alt_trans_haz`)."""
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import Tensor, nn
 from torch.nn.utils import parametrize
@@ -24,6 +26,8 @@ MAX_REF_COUNT, MIN_ALT_COUNT, MAX_ALT_COUNT, COUNT_BIN_SKIP = 10, 1, 15, 3
 NUM_REF_COUNT_BINS = (MAX_REF_COUNT // COUNT_BIN_SKIP) + 1
 NUM_ALT_COUNT_BINS = ((MAX_ALT_COUNT - MIN_ALT_COUNT) // COUNT_BIN_SKIP) + 1
 BETA_BASIS_SHAPES = ((1.0, 1.0), (1.0, 5.0), (5.0, 1.0), (5.0, 5.0))  # reference downsampler.py:27 (the kernels use the same)
+# torch.optim.AdamW's defaults, with which the balance fit's optimizer is built (reference downsampler.py:143): the device fit's hyperparameters
+ADAMW_DEFAULTS = {"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2}
 
 
 def ref_count_bin_indices(counts: Tensor) -> Tensor:
@@ -104,8 +108,16 @@ class Downsampler(nn.Module):
     def optimize_downsampling_balance(self, counts_slvra: Tensor, steps: int = 10000):
         """Reference :141-158: AdamW (torch defaults) on the two `.original` weight tensors, minimising the sum over
         (source, label, variant type) of the squared normalised expected downsampled counts -- i.e. spreading them evenly
-        over the ref / alt count bins.  Deterministic; runs where the module lives (a few seconds on the CPU)."""
+        over the ref / alt count bins.  Deterministic.
+
+        A float32 module on a ROCm device makes ONE library call (pmt_downsample_fit: a wavefront per cell runs every step on-chip)
+        and returns the per-cell losses [15 S][2] (before, after) as a device tensor; its weights give the torch fit's expected
+        downsampled counts and loss to ~1e-6 but are not the same numbers (the loss has flat directions along which rounding
+        decides where AdamW drifts).  A module on the CPU -- or any module under PMT_DOWNSAMPLER_FIT=torch, or one that is not
+        float32 -- runs the torch loop below (a few seconds on the CPU; pinned by tests/golden/downsampler_fit.npz) and returns None."""
         params = self.weights_parameters()
+        if params[0].device.type == "cuda" and params[0].dtype == torch.float32 and os.environ.get("PMT_DOWNSAMPLER_FIT", "") != "torch":
+            return self._fit_on_device(counts_slvra, steps)
         for p in params:
             p.requires_grad_(True)
         optimizer = torch.optim.AdamW([p for p in self.parameters() if p.requires_grad])
@@ -118,13 +130,7 @@ class Downsampler(nn.Module):
             torch.set_num_threads(min(threads, 4))
         try:
             for _ in range(steps):
-                expected = self.calculate_expected_downsampled_counts(counts_slvra)
-                total = torch.sum(expected, dim=(-2, -1), keepdim=True)
-                # a (source, label, variant type) cell without any data: the reference divides 0 / 0 there and every weight turns
-                # NaN; here such a cell contributes nothing (its weights only see the weight decay).  Cells with data are
-                # independent terms of the loss, so wherever the reference's result is finite this is the same fit.
-                normalized = expected / torch.where(total > 0, total, torch.ones_like(total))
-                loss = torch.sum(torch.sum(torch.square(normalized), dim=(-2, -1)))
+                loss = self.balance_loss(counts_slvra)
                 optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 optimizer.step()
@@ -132,6 +138,40 @@ class Downsampler(nn.Module):
             torch.set_num_threads(threads)
         for p in params:
             p.requires_grad_(False)
+
+    def balance_loss(self, counts_slvra: Tensor) -> Tensor:
+        """The loss of the balance fit at the module's present weights (`counts_slvra`: on the module's device, in its dtype)."""
+        expected = self.calculate_expected_downsampled_counts(counts_slvra)
+        total = torch.sum(expected, dim=(-2, -1), keepdim=True)
+        # a (source, label, variant type) cell without any data: the reference divides 0 / 0 there and every weight turns
+        # NaN; here such a cell contributes nothing (its weights only see the weight decay).  Cells with data are
+        # independent terms of the loss, so wherever the reference's result is finite this is the same fit.
+        normalized = expected / torch.where(total > 0, total, torch.ones_like(total))
+        return torch.sum(torch.sum(torch.square(normalized), dim=(-2, -1)))
+
+    def _fit_on_device(self, counts_slvra: Tensor, steps: int) -> Tensor:
+        """pmt_downsample_fit with torch.optim.AdamW's defaults (the ones the torch loop's optimizer is built with).  The kernel fits
+        scratch copies that are then `copy_`-ed into the parameters: a write through data_ptr() would not advance their `_version`,
+        which `weight_tables` keys its cache on."""
+        from permutect_amd.engine import lib as L  # (here: the module itself needs no built library on the CPU)
+        o_r, o_a = self.weights_parameters()
+        dev = o_r.device
+        if tuple(counts_slvra.shape) != tuple(o_r.shape[:-1]):
+            raise ValueError(f"counts_slvra has shape {tuple(counts_slvra.shape)}, the downsampler's cells are {tuple(o_r.shape[:-1])}")
+        counts = counts_slvra.detach().to(device=dev, dtype=torch.float32).contiguous()
+        ref_trans = self.binned_ref_trans_kry.detach().to(torch.float32).contiguous()
+        alt_trans = self.binned_alt_trans_haz.detach().to(torch.float32).contiguous()
+        ref, alt = o_r.detach().clone(memory_format=torch.contiguous_format), o_a.detach().clone(memory_format=torch.contiguous_format)
+        losses = torch.empty(o_r.shape[0] * o_r.shape[1] * o_r.shape[2], 2, dtype=torch.float32, device=dev)
+        hyper = ADAMW_DEFAULTS
+        with torch.cuda.device(dev):
+            L.check(L.load().pmt_downsample_fit(counts.data_ptr(), int(o_r.shape[0]), ref_trans.data_ptr(), alt_trans.data_ptr(), ref.data_ptr(),
+                                                alt.data_ptr(), int(steps), hyper["lr"], hyper["betas"][0], hyper["betas"][1], hyper["eps"],
+                                                hyper["weight_decay"], losses.data_ptr(), L.raw_stream(dev)), "pmt_downsample_fit")
+            with torch.no_grad():
+                o_r.copy_(ref)
+                o_a.copy_(alt)
+        return losses
 
     def calculate_downsampling_fractions(self, batch: Batch):
         """Reference :105-123, in torch (multinomial over the mixture, then a Beta draw)."""

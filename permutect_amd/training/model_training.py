@@ -10,6 +10,7 @@ tensorboard and the worst-offender report of the reference are out of scope (SUR
 from __future__ import annotations
 
 import math
+import time
 from typing import Optional
 
 import numpy as np
@@ -93,8 +94,11 @@ def training_params_fit_downsampler(training_params) -> bool:
 def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Optional[ReadsDataset],
                          training_params: TrainingParameters, chunk_variants: Optional[int] = 1 << 18, seed: int = 0,
                          dist=None, log=print, fix_alt_gather: bool = False, evaluate_every_epoch: bool = True,
-                         evaluations: Optional[list] = None):
-    """`fix_alt_gather`: the reference's DownsampledBatch gathers the kept alt reads without the offset of the ref region
+                         evaluations: Optional[list] = None, timing_log=None):
+    """`timing_log`: where the wall-time lines go (`downsampler fit: ...`, `epochs: ...`); None (the default): nowhere, so that callers
+    that do not ask for them see what they saw before.  They do not go through `log`, whose lines are one per epoch half, evaluation
+    pass and rollback and are counted as such (tests/test_dataset_gpu.py); the training CLI passes its `log` for both.
+    `fix_alt_gather`: the reference's DownsampledBatch gathers the kept alt reads without the offset of the ref region
     (SURVEY 0.5b), so its training steps see ref rows in place of alt reads; False reproduces that, True gathers the
     intended rows."""
     device = model._device
@@ -106,12 +110,21 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
             ds.pin_memory_if_it_fits()
     num_sources = train_dataset.validate_sources()  # (reference :63)
     balancer = Balancer(num_sources=num_sources, device=device)
-    downsampler = Downsampler(num_sources=num_sources)
+    timing_log = timing_log if timing_log is not None else (lambda *_: None)
+    downsampler = Downsampler(num_sources=num_sources).to(device)  # before the fit: a module on the device fits there (pmt_downsample_fit)
     if training_params_fit_downsampler(training_params):
-        # reference :58-60: fit the Beta-mixture weights so that the downsampled counts spread over the count bins
-        # (deterministic, on the CPU: ~15 s of tiny einsums; identical on every rank, which all see the whole dataset's totals)
-        downsampler.optimize_downsampling_balance(train_dataset.totals_slvra)
-    downsampler = downsampler.to(device)
+        # reference :58-60: fit the Beta-mixture weights so that the downsampled counts spread over the count bins.  On the device it is
+        # one deterministic launch (no atomics, nothing between workgroups: bit-identical from run to run) on the whole dataset's
+        # totals, which every rank sees -- so every rank runs the same launch on the same numbers and gets the same weights, and no
+        # collective is needed; a module on the CPU (or PMT_DOWNSAMPLER_FIT=torch) runs the torch loop, as deterministic, in ~15 s
+        totals_slvra = train_dataset.totals_slvra  # (one pass over the dataset's tables, cached: not the fit's time)
+        t_fit = time.perf_counter()
+        cell_losses = downsampler.optimize_downsampling_balance(totals_slvra)
+        if cell_losses is not None:
+            cells, (before, after) = cell_losses.shape[0], cell_losses.double().sum(dim=0).tolist()  # (.tolist(): waits for the launch)
+            timing_log(f"downsampler fit: {cells} cells, loss {before:.6f} -> {after:.6f}, {time.perf_counter() - t_fit:.2f} s")
+        else:
+            timing_log(f"downsampler fit (torch): {num_sources * 15} cells, {time.perf_counter() - t_fit:.2f} s")
     model.reset_source_predictor(num_sources)
     opt = FusedClipAdamW(model, lr=training_params.learning_rate, weight_decay=training_params.weight_decay)
     scheduler = PlateauScheduler(opt, min_lr=training_params.learning_rate / 100)
@@ -128,6 +141,7 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
     evaluations = [] if evaluations is None else evaluations
     last_epoch = training_params.num_epochs + training_params.num_calibration_epochs
     step_seed = seed * 1_000_003 + rank
+    t_epochs = time.perf_counter()
 
     for epoch in range(1, last_epoch + 1):
         is_calibration = epoch > training_params.num_epochs
@@ -204,6 +218,7 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
                         rollback = rank0_decides(rollback, device)
                     if rollback and checkpoint.load_checkpoint():
                         log(f"epoch {epoch}: loss diverged, restored the best checkpoint")
+    timing_log(f"epochs: {last_epoch} in {time.perf_counter() - t_epochs:.2f} s")
     if dist is not None:
         assert_replicas_identical(model.engine().space.theta)
     return history
