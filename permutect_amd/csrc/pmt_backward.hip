@@ -16,25 +16,9 @@
 // Replaces autograd over reference artifact_model.py:239-297 (misc_utils.py:127 `loss.backward()`).
 // Wave shape: 8 waves x 2 read tiles (2 waves per SIMD, 256 VGPRs each).  VALU instructions only address the 256
 // architectural VGPRs, so a 512-register "fat wave" (4 x 4) just shuffles values through AGPRs: measured slower.
-// PMT_BWD_RT = 1 (experimental build, `make EXTRA=-DPMT_BWD_RT=1`): the same 16-tile groups on SIXTEEN waves of one tile each, 128 registers,
-// four waves per SIMD -- twice the waves to hide a phase's latency behind; the weight-gradient exchange pairs neighbouring waves' tiles
-// into the 32 reads of one MFMA (16-bit stores into the halves of the dwords the two-tile form writes whole).
-#ifndef PMT_BWD_RT
-#define PMT_BWD_RT 2
-#endif
-#if PMT_BWD_RT == 1
-#define PMT_WAVES (2 * PMT_GROUP_WAVES)
-#define PMT_RT 1
-#define PMT_AUX_CAP 160  // (16 slabs: the LDS budget)
-#define PMT_BWD_WAVES_PER_SIMD 4
-#ifndef PMT_BWD_FRAG_AHEAD
-#define PMT_BWD_FRAG_AHEAD 2
-#endif
-#else
 #define PMT_WAVES PMT_GROUP_WAVES
 #define PMT_RT 2
 #define PMT_BWD_WAVES_PER_SIMD 2
-#endif
 #ifndef PMT_BWD_PIECES
 #define PMT_BWD_PIECES 3  // pieces of the products that keep the forward's precision (the head's recomputation); the input-gradient and
                           // recomputation products of the layers take PMT_DGRAD_PIECES / PMT_RECOMPUTE_PIECES (pmt_bwd_device.hpp)
@@ -213,7 +197,7 @@ DEV void backward_group(
     c.priv = priv;
     if (PMT_BWD_TRACE && bt.debug_flags && uniform(bt.debug_flags[2]) == grp + 1) c.trace = bt.debug_flags + 64 + wave * 512;
     trace_ev(c, 1);
-    c.wbase = stage_wbase(lane) + (PMT_RT == 1 ? 2 * (wave & 1) : 0);  // (one tile per wave: the odd wave of a pair writes the upper halves)
+    c.wbase = stage_wbase(lane);
     c.rbase = stage_rbase(lane);
     c.pf_sink = (c.dbg & 64) ? &sh.pf_sink[0] : nullptr;  // stash prefetch: OFF (measured slower, see DESIGN)
     const unsigned long long t_kernel0 = prof_now();

@@ -644,37 +644,17 @@ DEV void stage_pair_bf16(char* const (&pj)[4], int off, f4 v0, f4 v1) {
     }
 }
 
-// One tile per wave (PMT_RT == 1): the wave writes ITS half of every dword of the pair's plane -- the same addresses, 16-bit stores (pj
-// carries the + 2 bytes of the odd wave).  Two positions share a conversion: the packed pair's low half goes out with ds_write_b16, its
-// high half with ds_write_b16_d16_hi.
-DEV void lds_store16(char* p, unsigned v) { *reinterpret_cast<unsigned short*>(p) = (unsigned short)v; }
-template <int PIECES = 3>
-DEV void stage_half_bf16(char* const (&pj)[4], int off, f4 v) {
-#pragma unroll
-    for (int j = 0; j < 4; j += 2) {
-        const unsigned hi = cvt_pk_bf16(v[j], v[j + 1]);
-        lds_store16(pj[j] + off, hi);
-        lds_store16(pj[j + 1] + off, hi >> 16);
-        if constexpr (PIECES != 1) {
-            const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xFFFF0000u);
-            const unsigned mid = cvt_pk_bf16(sub_f32(v[j], h0), sub_f32(v[j + 1], h1));
-            lds_store16(pj[j] + off + 1024, mid);
-            lds_store16(pj[j + 1] + off + 1024, mid >> 16);
-        }
-    }
-}
-
 #define PMT_BF_PLANE_BYTES 2048  // hi + mid piece of one (wave, plane)
 #define PMT_ABL(c, bit) (PMT_BWD_ABLATE && ((c).dbg & (bit)))
 template <int NTO, int NTI, int SIDES, int BF = 3>
 DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, const f4 (&dy)[PMT_RT][NTO],
                            const f4 (&x)[PMT_RT][NTI], float scale) {
-    static_assert(PMT_RT == 2 || PMT_RT == 1, "a wave's two tiles, or the tiles of a pair of waves, are the 32 reads of one MFMA");
+    static_assert(PMT_RT == 2 && NTO > 0, "a wave's two tiles are the 32 reads of one MFMA");  // (checked where it is instantiated: pmt_cnn2.hip includes this header with one tile per wave)
     if (c.dbg & 1) return;
     constexpr int PIECES = PMT_BF_PIECES(BF);
     constexpr bool PRIV = (BF & PMT_BF_PRIV) != 0;  // c.priv != nullptr, as a compile-time fact
     constexpr int P = NTO + NTI, NB = NTO * NTI;
-    constexpr int NSLOT = PMT_WG_TILES / 2;  // operand slots of the stage: one per 32 reads (a wave; with one tile per wave a pair of waves)
+    constexpr int NSLOT = PMT_WG_TILES / 2;  // operand slots of the stage: one per 32 reads (a wave)
     constexpr bool COLS = SIDES == 1 && PMT_WAVES % NTI == 0;  // one linear whose columns of blocks divide the waves (1, 2, 4, 8 input tiles)
     constexpr int PW_CAP = (PMT_STAGE_PLANES * 1024) / (P * PMT_BF_PLANE_BYTES);          // waves whose operands fit the stage
     constexpr int PW = PW_CAP < NSLOT ? PW_CAP : NSLOT;
@@ -688,7 +668,7 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
     constexpr int TPW = COLS ? (NTO + ROWS - 1) / ROWS : (SIDES * NB + PMT_WAVES - 1) / PMT_WAVES;
     constexpr bool ALL_TASKS = COLS ? NTO % ROWS == 0 : (SIDES * NB) % PMT_WAVES == 0;  // every wave has TPW blocks: no "is there a block" branches
     const int lane = pmt_tid() & 63, g = lane >> 4, wave = uniform((int)(pmt_tid() >> 6));
-    const int my_slot = PMT_RT == 2 ? wave : wave >> 1, wr_s = PMT_RT == 2 ? c.wr : c.wr >> 1;  // (GroupGeom.wr is even with one tile per wave)
+    const int my_slot = wave, wr_s = c.wr;
     int t_ot[TPW], t_it[TPW], t_side[TPW];
     f4 acc[TPW], accb[TPW];
 #pragma unroll
@@ -741,17 +721,10 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
                      a2 = (unsigned)(size_t)(mine + (c.wbase ^ 32)), a3 = (unsigned)(size_t)(mine + (c.wbase ^ 48));
             asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
             char* const pj[4] = {lds_ptr(a0), lds_ptr(a1), lds_ptr(a2), lds_ptr(a3)};
-            if constexpr (PMT_RT == 2) {
 #pragma unroll
-                for (int ot = 0; ot < NTO; ++ot) stage_pair_bf16<PIECES>(pj, ot * PMT_BF_PLANE_BYTES, dy[0][ot], dy[PMT_RT - 1][ot]);
+            for (int ot = 0; ot < NTO; ++ot) stage_pair_bf16<PIECES>(pj, ot * PMT_BF_PLANE_BYTES, dy[0][ot], dy[PMT_RT - 1][ot]);
 #pragma unroll
-                for (int it = 0; it < NTI; ++it) stage_pair_bf16<PIECES>(pj, (NTO + it) * PMT_BF_PLANE_BYTES, x[0][it], x[PMT_RT - 1][it]);
-            } else {
-#pragma unroll
-                for (int ot = 0; ot < NTO; ++ot) stage_half_bf16<PIECES>(pj, ot * PMT_BF_PLANE_BYTES, dy[0][ot]);
-#pragma unroll
-                for (int it = 0; it < NTI; ++it) stage_half_bf16<PIECES>(pj, (NTO + it) * PMT_BF_PLANE_BYTES, x[0][it]);
-            }
+            for (int it = 0; it < NTI; ++it) stage_pair_bf16<PIECES>(pj, (NTO + it) * PMT_BF_PLANE_BYTES, x[0][it], x[PMT_RT - 1][it]);
         }
         prof_add(c, 18, t1);
         t1 = prof_now();

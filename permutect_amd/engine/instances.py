@@ -10,11 +10,12 @@ the library whose tile counts the model fills:
   * the default library, when the model fills ITS tiles (pmt_shape_id != 0);
   * a library under permutect_amd/instances/ with the model's tile counts (the widths compiled in when they are the model's, read at
     run time otherwise: pmt_shape_id 2 or 6): `make -C permutect_amd/csrc instances` builds the table of known shapes ahead of time
-    (the reference's test configuration T0), `__graft_entry__.build()` calls it;
+    (the reference's test configuration T0), `__graft_entry__.build()` builds them with every other variant (`make variants`);
   * the WIDE build (`make wide`: activations up to 128 features, generic instances only) for a model with a layer wider than 64;
-  * a library built on the spot (`make instance SHAPE=...`, one to two minutes, kept for later runs) unless PMT_JIT=0 or there is no
-    hipcc -- then, and for a model that cannot fill any tile shape (a read MLP that does not start, or a reducer that does not end,
-    with a Linear; widths beyond 64), the default library's generic instance, with a warning that says so.
+  * a library built on the spot (`make instance SHAPE=...`, one to two minutes, kept for later runs; objects under csrc/obj/, or
+    library and objects under PMT_INSTANCE_DIR) unless PMT_JIT=0 or there is no hipcc -- then, and for a model that cannot fill any
+    tile shape (a read MLP that does not start, or a reducer that does not end, with a Linear; widths beyond 64), the default
+    library's generic instance, with a warning that says so.
 """
 from __future__ import annotations
 
@@ -74,7 +75,7 @@ def exact_shape_of(desc: L.PmtModel) -> Optional[Tuple[int, ...]]:
 
 class _BuildLock:
     """One build at a time per tree (the ranks of a data-parallel job lower the same model at the same moment: they would all run `make` in
-    the same object directory).  An advisory lock on a file next to the objects; whoever gets it second finds the library built.
+    the same object directory).  An advisory lock on a file in the object directory; whoever gets it second finds the library built.
     (flock does not serialise the nodes of a job on a shared file system: give each node its own PMT_INSTANCE_DIR there.)"""
 
     def __init__(self, directory: str):
@@ -92,6 +93,49 @@ class _BuildLock:
         fcntl.flock(self.f, fcntl.LOCK_UN)
         self.f.close()
         return False
+
+
+def build_jobs(cap: int) -> int:
+    """Compilations at a time: this process's CPU allowance -- MAX_JOBS when the environment sets it, else its CPU affinity bounded by
+    its cgroup quota (the host's core count is not the job's) -- and at most `cap` (a backward translation unit takes 2 - 4 GB while it
+    compiles)."""
+    if os.environ.get("MAX_JOBS", "").isdigit() and int(os.environ["MAX_JOBS"]) > 0:
+        n = int(os.environ["MAX_JOBS"])
+    else:
+        try:
+            n = len(os.sched_getaffinity(0))
+        except (AttributeError, OSError):
+            n = os.cpu_count() or 1
+        try:
+            with open("/sys/fs/cgroup/cpu.max") as f:
+                quota, period = f.read().split()[:2]
+            if quota != "max":
+                n = min(n, max(1, int(quota) // int(period)))
+        except (OSError, ValueError):
+            pass
+    return max(1, min(n, cap))
+
+
+class BuildUnavailable(L.PmtError):
+    """nothing is built here: PMT_JIT=0, or no hipcc / make"""
+
+
+def _make(target: str, path: str, what: str, log, *variables: str) -> None:
+    """`make -C csrc <target>` (csrc/Makefile) under the build lock -- a no-op when `path` is up to date with the sources.  Raises
+    BuildUnavailable when nothing may be built here, PmtError when the build fails."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if os.environ.get("PMT_JIT", "1") == "0" or not (os.path.exists(hipcc) or shutil.which("hipcc")) or not shutil.which("make"):
+        raise BuildUnavailable(f"{what} cannot be built here (PMT_JIT=0, or no hipcc / make): `make -C permutect_amd/csrc {target}` builds it")
+    cmd = ["make", "-C", CSRC, f"-j{build_jobs(8)}", target, *variables]
+    try:  # (the lock lies where the objects go: PMT_INSTANCE_DIR for a shape built on the spot)
+        with _BuildLock((target == "instance" and cache_dir()) or os.path.join(CSRC, "obj")):
+            if not os.path.exists(path):
+                log(f"permutect_amd: building {what} (once) ...")
+            res = subprocess.run(cmd, capture_output=True, text=True)
+    except OSError as exc:
+        raise L.PmtError(f"permutect_amd: cannot build {what} here ({exc}); set PMT_INSTANCE_DIR to a writable directory")
+    if res.returncode != 0 or not os.path.exists(path):
+        raise L.PmtError(f"permutect_amd: building {what} failed:\n" + res.stderr[-2000:])
 
 
 def _tag(shape) -> str:
@@ -115,28 +159,17 @@ def is_current(path: str) -> bool:
 
 
 def build_instance(shape, log=print) -> Optional[str]:
-    """`make instance SHAPE=...` (csrc/Makefile) -- a no-op when the library is up to date with the sources; returns the library's path,
-    None when it cannot be built here (PMT_JIT=0, no hipcc / make, a read-only tree without PMT_INSTANCE_DIR)"""
-    if os.environ.get("PMT_JIT", "1") == "0":
-        return None
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which("hipcc")) or not shutil.which("make"):
-        return None
-    out = cache_dir()
-    path = os.path.join(out or INSTANCE_DIR, f"libpermutect_amd_{_tag(shape)}.so")
-    cmd = ["make", "-C", CSRC, f"-j{min(8, os.cpu_count() or 1)}", "instance", "SHAPE=" + " ".join(str(int(v)) for v in shape)]
-    if out:  # objects and library outside the package (command-line variables override the Makefile's)
-        cmd += [f"IDIR={os.path.join(out, 'inst_' + _tag(shape))}", f"ILIB={path}"]
+    """`make instance SHAPE=...` (csrc/Makefile; with PMT_INSTANCE_DIR set, library and objects go there) -- a no-op when the library is
+    up to date with the sources; returns the library's path, None when it cannot be built here (PMT_JIT=0, no hipcc / make, a read-only
+    tree without PMT_INSTANCE_DIR)"""
+    path = os.path.join(cache_dir() or INSTANCE_DIR, f"libpermutect_amd_{_tag(shape)}.so")
     try:
-        with _BuildLock(out or CSRC):
-            if not os.path.exists(path):
-                log(f"permutect_amd: building the kernel instances for model shape {shape} (once; ~1-2 minutes, ~4 with more than four tiles) ...")
-            res = subprocess.run(cmd, capture_output=True, text=True)
-    except OSError as exc:
-        warnings.warn(f"permutect_amd: cannot build kernel instances here ({exc}); set PMT_INSTANCE_DIR to a writable directory")
+        _make("instance", path, f"the kernel instances for model shape {shape} (~1-2 minutes, ~4 with more than four tiles)", log,
+              "SHAPE=" + " ".join(str(int(v)) for v in shape))
+    except BuildUnavailable:
         return None
-    if res.returncode != 0 or not os.path.exists(path):
-        warnings.warn("permutect_amd: building the kernel instances failed:\n" + res.stderr[-2000:])
+    except L.PmtError as exc:
+        warnings.warn(str(exc))
         return None
     return path
 
@@ -164,16 +197,8 @@ def wide_library(log=print, half32: bool = False) -> C.CDLL:
     `make wide` / `make wide32` when it is missing"""
     path, target = (WIDE32_LIB, "wide32") if half32 else (WIDE_LIB, "wide")
     if not os.path.exists(path):
-        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        if os.environ.get("PMT_JIT", "1") == "0" or not (os.path.exists(hipcc) or shutil.which("hipcc")) or not shutil.which("make"):
-            raise L.PmtError(f"this model (a layer wider than {L.MAX_WIDTH}, or d_ffn / 2 beyond {L.MAX_HALF_FFN}) needs the {target} build of the "
-                             f"library, `make -C permutect_amd/csrc {target}` (not built here, and PMT_JIT=0 or no hipcc / make to build it now)")
-        with _BuildLock(CSRC):
-            if not os.path.exists(path):  # (else: another process built it while this one waited for the lock)
-                log(f"permutect_amd: building the {target} library (once, ~3 minutes) ...")
-                res = subprocess.run(["make", "-C", CSRC, f"-j{min(8, os.cpu_count() or 1)}", target], capture_output=True, text=True)
-                if res.returncode != 0 or not os.path.exists(path):
-                    raise L.PmtError(f"building the {target} library failed:\n" + res.stderr[-2000:])
+        _make(target, path, f"the {target} library (~3 minutes; for a model with a layer wider than {L.MAX_WIDTH}, or d_ffn / 2 beyond "
+              f"{L.MAX_HALF_FFN})", log)
     return L.load(path)
 
 

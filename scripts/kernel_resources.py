@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / LDS / spill figures of every kernel in a built object, read from the code object's metadata notes.
-usage: scripts/kernel_resources.py permutect_amd/csrc/pmt_forward.o [name regex]"""
+usage: scripts/kernel_resources.py permutect_amd/csrc/obj/default/pmt_forward.o [name regex]"""
 import re
 import subprocess
 import sys
