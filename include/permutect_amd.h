@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PMT_ABI_VERSION 11
+#define PMT_ABI_VERSION 12
 
 /* bits of the fault word (PmtBatch.join_fault) */
 #define PMT_FAULT_JOIN 1
@@ -400,6 +400,25 @@ int pmt_downsample_index(const PmtDownsample* args, const float* ref_fracs, cons
 int pmt_downsample_fit(const float* counts_slvra, int32_t num_sources, const float* ref_trans_kry, const float* alt_trans_haz,
                        float* ref_logits_slvrak, float* alt_logits_slvrah, int32_t steps, double lr, double beta1, double beta2,
                        double eps, double weight_decay, float* loss_before_after, void* stream);
+
+/* The fit of the artifact allele-fraction spectra after refinement (reference architecture/spectra/artifact_spectra.py:58-75,
+ * `ArtifactSpectra.fit`, called from tools/refine_artifact_model.py:46-52: epochs of batch-64 torch.optim.Adam steps on 30 parameters,
+ * ~30 ATen ops each) as ONE persistent launch.  The loss of a step is minus the mean over its minibatch of the beta-binomial
+ * log-likelihoods (utils/stats_utils.py:28-40) under the (alpha, beta) of each row's (depth bin, variant type) cell, and Adam is
+ * element-wise, so the 3 x 5 cells are independent chains over one minibatch schedule: a wavefront per cell runs all
+ * epochs * ceil(n / batch_size) steps with its two raw parameters and their moments in registers.  Only the gradient is evaluated
+ * (digamma differences; no lgamma).  No atomics and nothing between workgroups: run-to-run bit-identical.
+ *   variant_types, depths, alt_counts [n]: the rows in the order the minibatches are cut from them (step t of an epoch takes rows
+ *   [t * batch_size, min((t + 1) * batch_size, n)); a short last batch divides by its own length).  Depth bin = (depth >= 10) +
+ *   (depth >= 20).  A row whose type is outside 0 .. 4 belongs to no cell; 0 <= alt count <= depth is the caller's to check.
+ *   log_alpha_dv, log_beta_dv [3][5]: the `.original` tensors of the exp parametrization (parameterizations.py:45-55), starting point
+ *   in, fitted values out.  Fresh moments; lr, beta1, beta2, eps are torch.optim.Adam's, no weight decay, nothing clipped
+ *   (misc_utils.py:125-129 is given no parameters to clip).  A cell without rows keeps its bits.
+ * n == 0 or epochs == 0: PMT_OK, nothing launched or written.  A NULL array, n < 0, batch_size < 1 or epochs < 0: PMT_E_INVALID,
+ * nothing launched. */
+int pmt_spectra_fit(const int32_t* variant_types, const int32_t* depths, const int32_t* alt_counts, int32_t n, float* log_alpha_dv,
+                    float* log_beta_dv, int32_t batch_size, int32_t epochs, double lr, double beta1, double beta2, double eps,
+                    void* stream);
 
 /* Per-variant losses (reference architecture/artifact_model.py:267-325). */
 typedef struct PmtLossArgs {

@@ -43,3 +43,5 @@ INFERENCE_BATCH_SIZE_NAME = "inference_batch_size"
 NUM_WORKERS_NAME = "num_workers"
 TENSORBOARD_DIR_NAME = "tensorboard_dir"
 PRETRAINED_ARTIFACT_MODEL_NAME = "pretrained_artifact_model"
+LEARN_ARTIFACT_SPECTRA_NAME = "learn_artifact_spectra"
+GENOMIC_SPAN_NAME = "genomic_span"
