@@ -304,7 +304,8 @@ int pmt_build_id(char* out, int32_t capacity);
 
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * 0 PmtModel, 1 PmtBatch, 2 PmtOutputs, 3 PmtOutputGrads, 4 PmtAdamW, 5 PmtLinear, 6 PmtOp, 7 PmtMlp, 8 PmtBlock, 9 PmtHead,
- * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs */
+ * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs, 16 PmtPosteriorRows,
+ * 17 PmtPosteriorParams */
 int pmt_struct_bytes(int which);
 
 /* Validates a descriptor against the kernels' limits. */
@@ -419,6 +420,53 @@ int pmt_downsample_fit(const float* counts_slvra, int32_t num_sources, const flo
 int pmt_spectra_fit(const int32_t* variant_types, const int32_t* depths, const int32_t* alt_counts, int32_t n, float* log_alpha_dv,
                     float* log_beta_dv, int32_t batch_size, int32_t epochs, double lr, double beta1, double beta2, double eps,
                     void* stream);
+
+/* The posterior model (reference architecture/posterior_model.py:69-157, posterior_model_priors.py:129-145,
+ * spectra/posterior_model_spectra.py:18-124, somatic_spectrum.py:72-96, normal_artifact_spectrum.py:37-58; this package's torch form:
+ * architecture/posterior_model.py): per candidate the log priors, the tumor and normal log-likelihoods and the log posteriors of the five
+ * calls (enums.Call: 0 somatic, 1 artifact, 2 seq error, 3 germline, 4 normal artifact), and the spectra's fit by minibatch Adam.  A lane
+ * per candidate; everything between the 48 bytes of a row and its outputs stays in registers.
+ *   rows: the candidates as device-resident columns of length n (permutect_amd/architecture/posterior_model.py: PosteriorRows).
+ *   contexts: ((i0 * 5 + i1) * 5 + i2) * 5 + i3 of the four centre bases of the haplotype row (left flank, ref, right flank, alt).
+ *   A variant type outside 0 .. 4 or a context outside 0 .. 624 is clamped into range (never an address out of bounds); counts are the
+ *   caller's to check (0 <= alt <= depth).
+ *   params.raw [PMT_POSTERIOR_RAW]: the `.original` tensors of the spectra, in this order:
+ *      0 ..  4  somatic cell fractions before the sigmoid          5 ..  9  somatic weight logits (before log_softmax)
+ *     10 .. 24  tumor artifact log alpha [3 depth bins][5 types]   25 .. 39  tumor artifact log beta
+ *     40 .. 54  normal spectrum log alpha [3][5]                   55 .. 69  normal spectrum log beta
+ *     70 .. 74  mean-multiplier logits [5] (before the sigmoid)    75 .. 79  log concentrations [5]
+ *   params.log_priors_vc [5 types][5 calls], params.snv_log_priors_rrra [625] (read where use_context != 0 and the row is an SNV). */
+#define PMT_POSTERIOR_RAW 80
+#define PMT_POSTERIOR_PARTIAL 128
+typedef struct PmtPosteriorRows {
+    int64_t n;
+    const int32_t *variant_types, *depths, *alt_counts, *normal_depths, *normal_alt_counts, *contexts;
+    const float *seq_error_log_lks, *normal_seq_error_log_lks, *allele_frequencies, *mafs, *normal_mafs, *artifact_logits;
+} PmtPosteriorRows;
+typedef struct PmtPosteriorParams {
+    const float *log_priors_vc, *snv_log_priors_rrra, *raw;
+    int32_t use_context, no_germline, has_het_beta;
+    float het_beta;
+} PmtPosteriorParams;
+/* One launch: the four [count][5] tensors of `log_posterior_and_ingredients` for rows [first, first + count); any output may be NULL.
+ * A NULL struct, column or parameter array, first < 0, count < 0 or first + count > n: PMT_E_INVALID, nothing launched.  count == 0:
+ * PMT_OK, nothing written. */
+int pmt_posterior_forward(const PmtPosteriorRows* rows, int64_t first, int64_t count, const PmtPosteriorParams* params, float* log_priors_bc,
+                          float* spectra_log_lks_bc, float* normal_log_lks_bc, float* log_posteriors_bc, void* stream);
+/* One minibatch's E step and gradient: for rows [first, first + count) the same quantities and, in the same pass, analytically, the
+ * gradient of -(1 / count) sum_b logsumexp_c(log_posteriors_bc) with respect to the 80 raw values, the softmax of every row added into
+ * totals[variant type][call], and sum_b of the log evidence.  Nothing per candidate is written: workgroup w of `num_partial_rows` walks
+ * its rows grid-stride and leaves partials[w][PMT_POSTERIOR_PARTIAL]: 0 .. 79 the gradient's share, 80 .. 104 the totals' [5][5],
+ * 105 the log evidence, the rest 0.  The sums inside a workgroup are taken in a fixed order (no atomics): run-to-run bit-identical.
+ * Invalid as above, or partials NULL, or num_partial_rows < 1: PMT_E_INVALID.  count == 0: PMT_OK, nothing written. */
+int pmt_posterior_step(const PmtPosteriorRows* rows, int64_t first, int64_t count, const PmtPosteriorParams* params, float* partials,
+                       int32_t num_partial_rows, void* stream);
+/* One workgroup: sums the partial rows in row order, applies torch.optim.Adam's update number `step` (1-based; bias corrections in
+ * double precision; no weight decay, nothing clipped) to raw / adam_m / adam_v [PMT_POSTERIOR_RAW], adds the 25 totals into
+ * totals_tc [5][5] and the summed log evidence into *loss_sum.  A NULL pointer, num_partial_rows < 1, count < 0 or step < 1:
+ * PMT_E_INVALID.  count == 0: PMT_OK, nothing written. */
+int pmt_posterior_update(const float* partials, int32_t num_partial_rows, int64_t count, float* raw, float* adam_m, float* adam_v, int64_t step,
+                         double lr, double beta1, double beta2, double eps, float* totals_tc, double* loss_sum, void* stream);
 
 /* Per-variant losses (reference architecture/artifact_model.py:267-325). */
 typedef struct PmtLossArgs {

@@ -40,6 +40,8 @@ extern "C" int pmt_struct_bytes(int which) {
         case 13: return (int)sizeof(PmtRecordArgs);
         case 14: return (int)sizeof(PmtBalanceArgs);
         case 15: return (int)sizeof(PmtEvalArgs);
+        case 16: return (int)sizeof(PmtPosteriorRows);
+        case 17: return (int)sizeof(PmtPosteriorParams);
         default: return PMT_E_INVALID;
     }
 }

@@ -27,6 +27,8 @@ READS_PACKED_U8, READS_F16, READS_F32 = 0, 1, 2
 OP_LINEAR, OP_SKIP = 0, 1
 SLOT_FLOATS = 4 * 256
 
+POSTERIOR_RAW, POSTERIOR_PARTIAL = 80, 128  # PMT_POSTERIOR_RAW, PMT_POSTERIOR_PARTIAL
+
 STEP_ON_DEVICE, STEP_SLOT = -1, 1000
 E_INVALID, E_UNSUPPORTED, E_CAPACITY, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4, -5
 _ERR = {-1: "invalid argument/descriptor", -2: "configuration not supported by the gfx950 kernels",
@@ -189,11 +191,22 @@ class PmtLossInputGrads(C.Structure):
     _fields_ = [("d_logits_b", vp), ("d_logits_bk", vp), ("d_alt_count_raw", vp), ("d_source_logits", vp)]
 
 
+class PmtPosteriorRows(C.Structure):
+    _fields_ = [("n", i64), ("variant_types", vp), ("depths", vp), ("alt_counts", vp), ("normal_depths", vp), ("normal_alt_counts", vp),
+                ("contexts", vp), ("seq_error_log_lks", vp), ("normal_seq_error_log_lks", vp), ("allele_frequencies", vp), ("mafs", vp),
+                ("normal_mafs", vp), ("artifact_logits", vp)]
+
+
+class PmtPosteriorParams(C.Structure):
+    _fields_ = [("log_priors_vc", vp), ("snv_log_priors_rrra", vp), ("raw", vp), ("use_context", i32), ("no_germline", i32),
+                ("has_het_beta", i32), ("het_beta", C.c_float)]
+
+
 EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", "pmt_limits", "pmt_struct_bytes", "pmt_model_check", "pmt_plan_groups", "pmt_plan_groups_device", "pmt_plan_device_chunks", "pmt_stash_bytes", "pmt_pack_params",
            "pmt_scan_counts", "pmt_forward", "pmt_backward", "pmt_clip_adamw",
            "pmt_dropout_mask", "pmt_rows_stash_bytes", "pmt_rows_forward", "pmt_rows_backward", "pmt_rows_workspace_floats", "pmt_cnn_forward", "pmt_cnn_backward", "pmt_cnn_stash_floats", "pmt_cnn_workspace_floats",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_record_losses", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_update", "pmt_record_losses", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -271,6 +284,9 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_downsample_index.argtypes = [P(PmtDownsample), vp, vp, vp, vp, vp, vp]
     lib.pmt_downsample_fit.argtypes = [vp, i32, vp, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     lib.pmt_spectra_fit.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+    lib.pmt_posterior_forward.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, vp, vp, vp, vp]
+    lib.pmt_posterior_step.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, i32, vp]
+    lib.pmt_posterior_update.argtypes = [vp, i32, i64, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     lib.pmt_balance_step.argtypes = [P(PmtBalanceArgs), vp]
     lib.pmt_record_evaluation.argtypes = [P(PmtEvalArgs), vp, vp]
     lib.pmt_posterior_rows.argtypes = [vp, i64, i32, i32, vp, vp, i32, vp, i32, vp, i64, vp]
@@ -288,7 +304,8 @@ def load(path: str = None) -> C.CDLL:
     if lib.pmt_abi_version() != ABI_VERSION:
         raise PmtError("libpermutect_amd.so ABI version mismatch; rebuild it")
     for which, st in enumerate([PmtModel, PmtBatch, PmtOutputs, PmtOutputGrads, PmtAdamW, PmtLinear, PmtOp, PmtMlp,
-                                PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs]):
+                                PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs,
+                                PmtPosteriorRows, PmtPosteriorParams]):
         if lib.pmt_struct_bytes(which) != C.sizeof(st):
             raise PmtError(f"ctypes layout of {st.__name__} ({C.sizeof(st)} B) does not match the library "
                            f"({lib.pmt_struct_bytes(which)} B)")

@@ -1,4 +1,4 @@
-"""Integer enums that are part of the Batch contract (reference permutect/utils/enums.py:4-9,30-39)."""
+"""Integer enums that are part of the Batch contract (reference permutect/utils/enums.py:4-9,22-39)."""
 import enum
 
 
@@ -8,6 +8,15 @@ class Variation(enum.IntEnum):
     DELETION = 2
     BIG_INSERTION = 3
     BIG_DELETION = 4
+
+
+class Call(enum.IntEnum):
+    """the posterior model's calls (reference permutect/utils/enums.py:22-27)"""
+    SOMATIC = 0
+    ARTIFACT = 1
+    SEQ_ERROR = 2
+    GERMLINE = 3
+    NORMAL_ARTIFACT = 4
 
 
 class Epoch(enum.IntEnum):

@@ -1,11 +1,20 @@
 """The artifact-model stage of `filter_variants` on the MI355X engine (reference tools/filter_variants.py:292-320, :350-357:
 `generate_posterior_data` + `MemoryMappedData.from_generator`): every candidate of a dataset tar goes through the model's forward and
 comes out as a read-less Datum row whose info array is its embedding and whose CACHED_ARTIFACT_LOGIT is its logit -- the input of
-the posterior model.  What stands in front of this stage in the reference (plain-text parsing, VCF annotation) and behind it (the
-posterior model, the filtered VCF) is out of scope: the tool reads a dataset tar in the reference's format and writes the
-posterior data as a tar in the same format.
+the posterior model.  What stands in front of this stage in the reference (plain-text parsing, VCF annotation) and the filtered VCF
+behind it are out of scope: the tool reads a dataset tar in the reference's format and writes the posterior data as a tar
+in the same format.
 
     python -m permutect_amd.tools.filter_variants --test_dataset_tar candidates.tar --artifact_model model.pt --output posterior.tar
+
+With `--genomic_span` the posterior stage follows (reference tools/filter_variants.py:244-289; architecture/posterior_model.py): rank 0
+turns the posterior data into device-resident columns, learns the priors and allele-fraction spectra
+(`PosteriorModel.learn_priors_and_spectra`; context-dependent SNV priors stay off in every epoch: the reference's pymc fit of them is not
+built), sets the error-probability threshold of every variant type and writes per-candidate probabilities, calls and the thresholds as
+arrays to `--calls_output` (.npz).  The artifact priors and spectra stored in the model file are loaded and, as in the reference
+(tools/filter_variants.py:242, :265), not used.
+
+    ... --genomic_span 3e9 --calls_output calls.npz [--num_spectrum_iterations 10] [--germline_mode | --no_germline_mode] [--het_beta B]
 
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N -m permutect_amd.tools.filter_variants ...`: WORLD_SIZE > 1) the
 candidates are cut into N contiguous shards, one process per GPU, no collective on the data path; rank 0 concatenates the shards'
@@ -26,6 +35,8 @@ from permutect_amd.training.distributed import init_from_env
 
 TEST_DATASET_TAR_NAME = "test_dataset_tar"
 ARTIFACT_MODEL_NAME = "artifact_model"  # (reference constants.py: ARTIFACT_MODEL_NAME)
+GENOMIC_SPAN_NAME = "genomic_span"       # (reference constants.py: GENOMIC_SPAN_NAME)
+POSTERIOR_BATCH_SIZE = 64               # the reference's loader for the posterior model takes its --batch_size, 64 by default
 DEFAULT_BATCH_SIZE = 65536  # the reference's flag defaults to 64 (tools/filter_variants.py:81); the rows do not depend on it
 
 
@@ -44,9 +55,56 @@ def main_without_parsing(args, log=print):
         log(f"{len(posterior)} candidates through the artifact model on {world} GPU(s) in {dt:.3f} s ({len(posterior) / max(dt, 1e-9) / 1e6:.2f} M/s, "
             "disk to posterior rows)")
         posterior.save_to_tarfile(getattr(args, constants.OUTPUT_NAME))
+        if posterior_stage_requested(args):  # (sequential: under torchrun the other ranks wait at the barrier below)
+            run_posterior_stage(args, posterior, device, log)
     if dist is not None:
         dist.barrier()
     return posterior
+
+
+def posterior_stage_requested(args) -> bool:
+    return getattr(args, GENOMIC_SPAN_NAME, None) is not None
+
+
+def posterior_outputs(model, rows, thresholds, losses, germline_mode: bool) -> dict:
+    """the arrays of `--calls_output`: per candidate the four ingredient tensors' first three, the posterior probabilities, the error
+    probability, whether it is filtered (reference `apply_filtering_to_vcf`, :535-537: error probability strictly above its variant
+    type's threshold) and the most probable call; the thresholds by variant type; the per-epoch losses; the model's state_dict"""
+    from permutect_amd.enums import Call, Variation
+    with torch.no_grad():
+        log_priors_bc, spectra_log_lks_bc, normal_log_lks_bc, log_posteriors_bc = model.log_posterior_and_ingredients(rows)
+        probs_bc = torch.nn.functional.softmax(log_posteriors_bc, dim=1)
+        error_probs_b = 1 - probs_bc[:, Call.GERMLINE if germline_mode else Call.SOMATIC]
+        thresholds_v = torch.tensor([thresholds[v] for v in Variation], dtype=error_probs_b.dtype, device=error_probs_b.device)
+        filtered_b = error_probs_b > thresholds_v[rows.variant_types.long()]
+        most_confident_call_b = torch.max(probs_bc, dim=-1).indices
+    out = {"posterior_probabilities_bc": probs_bc, "error_probabilities_b": error_probs_b, "log_priors_bc": log_priors_bc,
+           "spectra_log_lks_bc": spectra_log_lks_bc, "normal_log_lks_bc": normal_log_lks_bc, "thresholds_v": thresholds_v,
+           "filtered_b": filtered_b, "most_confident_call_b": most_confident_call_b, "losses": torch.tensor(losses, dtype=torch.float64)}
+    out.update(model.state_dict())
+    return {k: v.detach().cpu().numpy() for k, v in out.items()}
+
+
+def run_posterior_stage(args, posterior: MemoryMappedData, device, log=print):
+    import numpy as np
+    from permutect_amd.architecture.posterior_model import PosteriorModel, PosteriorRows
+    germline_mode, no_germline_mode = getattr(args, "germline_mode", False), getattr(args, "no_germline_mode", False)
+    if germline_mode and no_germline_mode:
+        raise ValueError("--germline_mode and --no_germline_mode are incompatible")
+    t0 = time.perf_counter()
+    rows = PosteriorRows.from_data(posterior, device=device)
+    n = len(rows)
+    model = PosteriorModel(getattr(args, "initial_log_variant_prior"), getattr(args, "initial_log_artifact_prior"),
+                           no_germline_mode=no_germline_mode, device=device, het_beta=getattr(args, "het_beta", None))
+    ratio = (getattr(args, GENOMIC_SPAN_NAME) - n) / n
+    losses = model.learn_priors_and_spectra(rows, getattr(args, "num_spectrum_iterations"), ratio,
+                                            learning_rate=getattr(args, "spectrum_learning_rate"), batch_size=POSTERIOR_BATCH_SIZE)
+    thresholds = model.calculate_probability_thresholds(rows, germline_mode=germline_mode, recall_weight=getattr(args, "recall_weight"))
+    out = posterior_outputs(model, rows, thresholds, losses, germline_mode)
+    np.savez(getattr(args, "calls_output"), **out)
+    log(f"posterior model: {n} candidates, {len(losses)} epochs in {time.perf_counter() - t0:.3f} s; thresholds "
+        f"{ {v.name: round(float(t), 4) for v, t in thresholds.items()} }; {int(out['filtered_b'].sum())} filtered")
+    return model, out
 
 
 def parse_arguments(argv=None):
@@ -56,7 +114,22 @@ def parse_arguments(argv=None):
     parser.add_argument("--" + constants.OUTPUT_NAME, type=str, required=True, help="output tar of the posterior data")
     parser.add_argument("--" + constants.BATCH_SIZE_NAME, type=int, default=DEFAULT_BATCH_SIZE, required=False, help="batch size")
     parser.add_argument("--chunk_variants", type=int, default=None, required=False, help="candidates per HBM-resident chunk (default: the loader's)")
-    return parser.parse_args(argv)
+    # the posterior stage (the reference's names and defaults, tools/filter_variants.py:83-163); without --genomic_span nothing of it runs
+    parser.add_argument("--" + GENOMIC_SPAN_NAME, type=float, default=None, required=False,
+                        help="number of sites considered by Mutect2, candidates or not: runs the posterior model behind the artifact model")
+    parser.add_argument("--calls_output", type=str, default=None, required=False, help="output .npz of the posterior stage (with --genomic_span)")
+    parser.add_argument("--num_spectrum_iterations", type=int, default=10, required=False, help="epochs of fitting the allele-fraction spectra")
+    parser.add_argument("--spectrum_learning_rate", type=float, default=0.001, required=False, help="learning rate of that fit")
+    parser.add_argument("--initial_log_variant_prior", type=float, default=-10.0, required=False, help="initial natural log prior of somatic variants")
+    parser.add_argument("--initial_log_artifact_prior", type=float, default=-10.0, required=False, help="initial natural log prior of artifacts")
+    parser.add_argument("--germline_mode", action="store_true", help="germline calls are not errors when the threshold is set")
+    parser.add_argument("--no_germline_mode", action="store_true", help="no germline calls: somatic, artifact and sequencing error only")
+    parser.add_argument("--het_beta", type=float, default=None, required=False, help="beta-binomial shape of the germline het spectrum instead of a binomial")
+    parser.add_argument("--recall_weight", type=float, default=1.0, required=False, help="weight of recall against precision in the F-beta score")
+    args = parser.parse_args(argv)
+    if posterior_stage_requested(args) and not args.calls_output:
+        parser.error("--genomic_span runs the posterior stage, which needs --calls_output")
+    return args
 
 
 def main():
