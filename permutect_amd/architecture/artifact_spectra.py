@@ -13,7 +13,6 @@ where it runs decides how:
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 from torch import Tensor, nn
@@ -22,22 +21,15 @@ from torch.nn.utils import parametrize
 from permutect_amd.architecture.modules import PositiveNumber
 from permutect_amd.engine import lib as L
 from permutect_amd.enums import Variation
+from permutect_amd.stats_utils import ADAM_DEFAULTS, beta_binomial_log_lk, fits_on_device
 
 DEPTH_CUTOFFS = [10, 20]
 NUM_DEPTH_BINS = len(DEPTH_CUTOFFS) + 1
-ADAM_DEFAULTS = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)  # torch.optim.Adam's, which the reference takes as they are
 
 
 def depths_to_depth_bins(depths_b: Tensor) -> Tensor:
     """the bin is the number of cutoffs that are met or exceeded (reference :22-24)"""
     return (depths_b >= DEPTH_CUTOFFS[0]).long() + (depths_b >= DEPTH_CUTOFFS[1]).long()
-
-
-def beta_binomial_log_lk(n: Tensor, k: Tensor, alpha: Tensor, beta: Tensor) -> Tensor:
-    """log P(k | n, alpha, beta), normalised (reference utils/stats_utils.py:28-40)"""
-    combinatorial_term = torch.lgamma(n + 1) - torch.lgamma(n - k + 1) - torch.lgamma(k + 1)
-    return (combinatorial_term + torch.lgamma(k + alpha) + torch.lgamma(n - k + beta) + torch.lgamma(alpha + beta)
-            - torch.lgamma(n + alpha + beta) - torch.lgamma(alpha) - torch.lgamma(beta))
 
 
 def check_fit_inputs(types_b: Tensor, depths_b: Tensor, alt_counts_b: Tensor) -> None:
@@ -87,7 +79,7 @@ class ArtifactSpectra(nn.Module):
         dev, dtype = raw[0].device, raw[0].dtype
         types_b, depths_b, alt_counts_b = types_b.to(dev), depths_b.to(dev), alt_counts_b.to(dev)  # (one upload each, wherever they were)
         check_fit_inputs(types_b, depths_b, alt_counts_b)
-        if dev.type == "cuda" and dtype == torch.float32 and os.environ.get("PMT_SPECTRA_FIT", "") != "torch":
+        if fits_on_device(raw[0], "PMT_SPECTRA_FIT"):
             return self._fit_on_device(num_epochs, types_b, depths_b, alt_counts_b, batch_size)
         types_b, depths_b, alt_counts_b = types_b.long(), depths_b.to(dtype), alt_counts_b.to(dtype)
         optimizer = torch.optim.Adam(self.parameters(), **ADAM_DEFAULTS)

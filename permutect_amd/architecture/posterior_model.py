@@ -17,7 +17,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import List, Optional
 
 import numpy as np
@@ -29,10 +28,10 @@ from permutect_amd.architecture.posterior_spectra import PosteriorModelSpectra
 from permutect_amd.data.datum import Data, HAPLOTYPES_START_IDX
 from permutect_amd.engine import lib as L
 from permutect_amd.enums import Call, Variation
+from permutect_amd.stats_utils import ADAM_DEFAULTS, fits_on_device
 
 INT_COLUMNS = ("variant_types", "depths", "alt_counts", "normal_depths", "normal_alt_counts", "contexts")
 FLOAT_COLUMNS = ("seq_error_log_lks", "normal_seq_error_log_lks", "allele_frequencies", "mafs", "normal_mafs", "artifact_logits")
-ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's, which the reference takes as they are
 MAX_PARTIAL_ROWS = 1024
 
 
@@ -131,8 +130,7 @@ class PosteriorModel(nn.Module):
 
     # ---- where it runs ---------------------------------------------------------------------------------------------------------
     def _on_device(self) -> bool:
-        p = self.priors.log_priors_vc
-        return p.device.type == "cuda" and p.dtype == torch.float32 and os.environ.get("PMT_POSTERIOR", "") != "torch"
+        return fits_on_device(self.priors.log_priors_vc, "PMT_POSTERIOR")
 
     def raw_spectra_parameters(self) -> List[Tensor]:
         """the eight `.original` tensors in the order of PmtPosteriorParams.raw (include/permutect_amd.h): 80 values"""
@@ -249,6 +247,7 @@ class PosteriorModel(nn.Module):
         totals = torch.zeros(max(num_iterations, 1), len(Variation), len(Call), dtype=torch.float32, device=dev)
         loss_sums = torch.zeros(max(num_iterations, 1), dtype=torch.float64, device=dev)
         lib, rows, step = L.load(), data.descriptor(), 0
+        (beta1, beta2), eps = ADAM_DEFAULTS["betas"], ADAM_DEFAULTS["eps"]  # (the learning rate is the caller's)
         with torch.cuda.device(dev), torch.no_grad():
             stream = L.raw_stream(dev)
             for epoch in range(num_iterations):
@@ -259,7 +258,7 @@ class PosteriorModel(nn.Module):
                     L.check(lib.pmt_posterior_step(C.byref(rows), first, count, C.byref(params), partials.data_ptr(), num_partial_rows, stream),
                             "pmt_posterior_step")
                     L.check(lib.pmt_posterior_update(partials.data_ptr(), num_partial_rows, count, raw.data_ptr(), adam_m.data_ptr(),
-                                                     adam_v.data_ptr(), step, lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
+                                                     adam_v.data_ptr(), step, lr, beta1, beta2, eps,
                                                      totals[epoch].data_ptr(), loss_sums[epoch:].data_ptr(), stream), "pmt_posterior_update")
                 self.priors.update_priors_m_step(totals[epoch], ratio)
             self.load_raw_spectra_parameters(raw)  # the fitted raw values back into the module

@@ -14,18 +14,13 @@ import torch
 from torch import Tensor, nn
 from torch.nn.utils import parametrize
 
-from permutect_amd.architecture.artifact_spectra import ArtifactSpectra, beta_binomial_log_lk
+from permutect_amd.architecture.artifact_spectra import ArtifactSpectra
 from permutect_amd.architecture.modules import BoundedNumber, LogWeights, PositiveNumber
 from permutect_amd.enums import Call, Variation
+from permutect_amd.stats_utils import beta_binomial_log_lk, binomial_log_lk
 
 NUM_SOMATIC_COMPONENTS = 5
 NUM_MIXTURE_POINTS = 100  # len(torch.arange(0.001, 0.999, 0.01)): the binomial mixture that stands for the uniform-binomial integral
-
-
-def binomial_log_lk(n: Tensor, k: Tensor, p: Tensor) -> Tensor:
-    """reference utils/stats_utils.py:21-25"""
-    combinatorial_term = torch.lgamma(n + 1) - torch.lgamma(n - k + 1) - torch.lgamma(k + 1)
-    return combinatorial_term + k * torch.log(p) + (n - k) * torch.log(1 - p)
 
 
 def uniform_binomial_log_lk(n: Tensor, k: Tensor, x1: Tensor, x2: Tensor) -> Tensor:

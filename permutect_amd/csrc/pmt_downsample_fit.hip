@@ -20,8 +20,8 @@
 // zero logits and take part in the sums with zeros; nothing is stored from them.
 //
 // No LDS, no barrier, no atomics, nothing between workgroups; the loop count is the launch argument.  Plain fp32 with expf and IEEE
-// division / square root.  AdamW's two bias corrections depend on the step number alone: lane j computes those of step t0 + j + 1 in
-// double precision (pow) once every 64 steps and a step reads its pair from its lane (v_readlane), so no running fp32 product.
+// division / square root.  The sums over the wave, AdamW's moment update and its per-lane table of bias corrections are
+// pmt_stats_device.hpp's (fit_sum32, fit_adam, FitSchedule); the weight decay `theta *= 1 - lr * weight_decay` comes first, here.
 //
 // A launch is a chain of `steps` dependent iterations of ~1 480 instructions on 20 lanes: it is bound by instruction LATENCY -- the
 // issue time of one wave's dependent stream (expf, division, the cross-lane sums) --, not by any throughput of the device.  The figure of
@@ -30,6 +30,7 @@
 #include <math.h>
 
 #include "permutect_amd.h"
+#include "pmt_stats_device.hpp"
 
 #define FIT_L 3
 #define FIT_V 5
@@ -37,27 +38,6 @@
 #define FIT_A 5
 #define FIT_K 4
 #define FIT_ENTRIES (FIT_R * FIT_A)  // 20 (r, a) entries per cell, one lane each
-
-struct FitHyper {
-    float decay;        // 1 - lr * weight_decay
-    float one_m_beta1;  // AdamW: m += (1 - beta1) (g - m)
-    float beta2, one_m_beta2, eps;
-    double lr, beta1, beta2_d;  // for the bias corrections
-};
-
-template <int CTRL>
-__device__ __forceinline__ float fit_dpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-// sum over lanes 0 .. 31 (lanes 32 .. 63 get the sum of their own half); every lane of a half ends with the same bits
-__device__ __forceinline__ float fit_sum32(float x) {
-    x += fit_dpp<0xB1>(x);   // quad_perm [1 0 3 2]
-    x += fit_dpp<0x4E>(x);   // quad_perm [2 3 0 1]
-    x += fit_dpp<0x141>(x);  // row_half_mirror: the other quad of the eight
-    x += fit_dpp<0x140>(x);  // row_mirror: the other eight of the sixteen
-    x += __shfl_xor(x, 16);
-    return x;
-}
 
 __device__ __forceinline__ void fit_softmax4(const float (&t)[FIT_K], float (&p)[FIT_K]) {
     const float mx = fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3]));
@@ -108,15 +88,14 @@ __device__ __forceinline__ float fit_forward(float c, const float (&tr)[FIT_K][F
     return loss;
 }
 
-__device__ __forceinline__ void fit_adamw(float& p, float& m, float& v, float g, const FitHyper& h, float step_size, float bc2_sqrt) {
-    p *= h.decay;
-    m += h.one_m_beta1 * (g - m);
-    v = h.beta2 * v + h.one_m_beta2 * g * g;
-    p -= step_size * (m / (sqrtf(v) / bc2_sqrt + h.eps));
+// torch.optim.AdamW: the decay (1 - lr * weight_decay), then Adam
+__device__ __forceinline__ void fit_adamw(float& p, float& m, float& v, float g, float decay, const FitAdam& h, float step_size, float bc2_sqrt) {
+    p *= decay;
+    fit_adam(p, m, v, g, h, step_size, bc2_sqrt);
 }
 
 __global__ __launch_bounds__(64) void pmt_downsample_fit_kernel(const float* __restrict__ counts, const float* __restrict__ ref_trans, const float* __restrict__ alt_trans,
-                                                                float* __restrict__ ref_logits, float* __restrict__ alt_logits, int steps, FitHyper hy, float* __restrict__ losses) {
+                                                                float* __restrict__ ref_logits, float* __restrict__ alt_logits, int steps, FitAdam hy, float decay, float* __restrict__ losses) {
     const int cell = blockIdx.x, lane = threadIdx.x;
     const bool owner = lane < FIT_ENTRIES;
     const int e = owner ? lane : 0, r = e / FIT_A, a = e % FIT_A;
@@ -139,7 +118,7 @@ __global__ __launch_bounds__(64) void pmt_downsample_fit_kernel(const float* __r
         m_r[k] = m_a[k] = v_r[k] = v_a[k] = 0.f;
     }
 
-    float step_size = 0.f, bc2_sqrt = 1.f;  // of step (t & ~63) + lane + 1
+    FitSchedule schedule;
     for (int t = 0;; ++t) {
         float pr[FIT_K], pa[FIT_K], u[FIT_R], w[FIT_A], n[FIT_R][FIT_A], tsafe;
         fit_softmax4(th_r, pr);
@@ -150,13 +129,8 @@ __global__ __launch_bounds__(64) void pmt_downsample_fit_kernel(const float* __r
             if (losses != nullptr && lane == 0) losses[2 * cell + 1] = loss;
             break;
         }
-        if ((t & 63) == 0) {
-            const double step = (double)(t + lane + 1);
-            step_size = (float)(hy.lr / (1.0 - pow(hy.beta1, step)));
-            bc2_sqrt = (float)sqrt(1.0 - pow(hy.beta2_d, step));
-        }
-        const float ss = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(step_size), t & 63));
-        const float bs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bc2_sqrt), t & 63));
+        float ss, bs;
+        schedule.at(hy, t & 63, (double)(t + lane + 1), ss, bs);
 
         // G = dloss / dE, folded at once into  gw[y] = sum_z G[y,z] w[z]  and  gu[z] = sum_y G[y,z] u[y]
         float gw[FIT_R], gu[FIT_A];
@@ -187,8 +161,8 @@ __global__ __launch_bounds__(64) void pmt_downsample_fit_kernel(const float* __r
         }
 #pragma unroll
         for (int k = 0; k < FIT_K; ++k) {
-            fit_adamw(th_r[k], m_r[k], v_r[k], pr[k] * (dpr[k] - dot_r), hy, ss, bs);
-            fit_adamw(th_a[k], m_a[k], v_a[k], pa[k] * (dpa[k] - dot_a), hy, ss, bs);
+            fit_adamw(th_r[k], m_r[k], v_r[k], pr[k] * (dpr[k] - dot_r), decay, hy, ss, bs);
+            fit_adamw(th_a[k], m_a[k], v_a[k], pa[k] * (dpa[k] - dot_a), decay, hy, ss, bs);
         }
     }
     if (owner && steps > 0) {
@@ -206,16 +180,8 @@ extern "C" int pmt_downsample_fit(const float* counts_slvra, int32_t num_sources
     if (!counts_slvra || !ref_trans_kry || !alt_trans_haz || !ref_logits_slvrak || !alt_logits_slvrah) return PMT_E_INVALID;
     if (num_sources < 1 || steps < 0 || steps > PMT_FIT_MAX_STEPS) return PMT_E_INVALID;
     if (steps == 0 && loss_before_after == nullptr) return PMT_OK;
-    FitHyper hy;
-    hy.decay = (float)(1.0 - lr * weight_decay);
-    hy.one_m_beta1 = (float)(1.0 - beta1);
-    hy.beta2 = (float)beta2;
-    hy.one_m_beta2 = (float)(1.0 - beta2);
-    hy.eps = (float)eps;
-    hy.lr = lr;
-    hy.beta1 = beta1;
-    hy.beta2_d = beta2;
+    const float decay = (float)(1.0 - lr * weight_decay);
     hipLaunchKernelGGL(pmt_downsample_fit_kernel, dim3((unsigned)num_sources * (FIT_L * FIT_V)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                       counts_slvra, ref_trans_kry, alt_trans_haz, ref_logits_slvrak, alt_logits_slvrah, (int)steps, hy, loss_before_after);
+                       counts_slvra, ref_trans_kry, alt_trans_haz, ref_logits_slvrak, alt_logits_slvrah, (int)steps, fit_adam_hyper(lr, beta1, beta2, eps), decay, loss_before_after);
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
 }

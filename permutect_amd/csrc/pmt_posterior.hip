@@ -12,7 +12,7 @@
 //     The background cluster BetaBinomial(k | n, 1, 1) is -log(n + 1) exactly;
 //   * the two three-way germline mixtures, the log_softmax of the priors and the softmax over the five calls in double (a few dozen
 //     operations);
-//   * with GRAD 18 fp32 digammas (pmt_posterior_math.hpp) for the three learned beta-binomials.
+//   * with GRAD 18 fp32 digammas (pmt_stats_device.hpp, as are the beta-binomial and Adam's update) for the three learned beta-binomials.
 // The transformed parameters (sigmoid, exp, log_softmax of the 80 raw values) and the 100 mixture points are computed once per workgroup
 // into LDS.
 //
@@ -25,7 +25,7 @@
 #include <math.h>
 
 #include "permutect_amd.h"
-#include "pmt_posterior_math.hpp"
+#include "pmt_stats_device.hpp"
 
 #define PO_WAVE 64
 #define PO_K 5        // somatic components
@@ -345,22 +345,17 @@ __global__ __launch_bounds__(PO_WAVE) void pmt_posterior_step_kernel(PmtPosterio
     out[lane + PO_WAVE] = lane + PO_WAVE < PMT_POSTERIOR_RAW ? acc[1] * scale : acc[1];
 }
 
-struct PoAdam {
-    float one_m_beta1, beta2, one_m_beta2, eps, step_size, bc2_sqrt;
-};
-
 __global__ __launch_bounds__(PMT_POSTERIOR_PARTIAL) void pmt_posterior_update_kernel(const float* __restrict__ partials, int num_partial_rows,
                                                                                     float* __restrict__ raw, float* __restrict__ adam_m,
-                                                                                    float* __restrict__ adam_v, PoAdam h,
+                                                                                    float* __restrict__ adam_v, FitAdam h, float step_size, float bc2_sqrt,
                                                                                     float* __restrict__ totals_tc, double* __restrict__ loss_sum) {
     const int j = threadIdx.x;
     float s = 0.f;
     for (int r = 0; r < num_partial_rows; ++r) s += partials[(size_t)r * PMT_POSTERIOR_PARTIAL + j];  // row order: the same sum in every run
     if (j < PMT_POSTERIOR_RAW) {  // torch.optim.Adam
-        float m = adam_m[j], v = adam_v[j];
-        m += h.one_m_beta1 * (s - m);
-        v = h.beta2 * v + h.one_m_beta2 * s * s;
-        raw[j] -= h.step_size * (m / (sqrtf(v) / h.bc2_sqrt + h.eps));
+        float p = raw[j], m = adam_m[j], v = adam_v[j];
+        fit_adam(p, m, v, s, h, step_size, bc2_sqrt);
+        raw[j] = p;
         adam_m[j] = m;
         adam_v[j] = v;
     } else if (j < PMT_POSTERIOR_RAW + PO_TYPES * PO_CALLS) {
@@ -410,14 +405,10 @@ extern "C" int pmt_posterior_update(const float* partials, int32_t num_partial_r
     if (!partials || !raw || !adam_m || !adam_v || !totals_tc || !loss_sum) return PMT_E_INVALID;
     if (num_partial_rows < 1 || count < 0 || step < 1) return PMT_E_INVALID;
     if (count == 0) return PMT_OK;
-    PoAdam h;
-    h.one_m_beta1 = (float)(1.0 - beta1);
-    h.beta2 = (float)beta2;
-    h.one_m_beta2 = (float)(1.0 - beta2);
-    h.eps = (float)eps;
-    h.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
-    h.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
+    const FitAdam h = fit_adam_hyper(lr, beta1, beta2, eps);
+    float step_size, bc2_sqrt;
+    fit_bias_corrections(h, (double)step, step_size, bc2_sqrt);  // on the host
     hipLaunchKernelGGL(pmt_posterior_update_kernel, dim3(1), dim3(PMT_POSTERIOR_PARTIAL), 0, reinterpret_cast<hipStream_t>(stream), partials,
-                       (int)num_partial_rows, raw, adam_m, adam_v, h, totals_tc, loss_sum);
+                       (int)num_partial_rows, raw, adam_m, adam_v, h, step_size, bc2_sqrt, totals_tc, loss_sum);
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
 }

@@ -11,8 +11,6 @@ bins; deterministic, pinned by tests/golden/downsampler_fit.npz).  Module layout
 (`parametrizations.log_ref_weights_slvrak.original`, ..., `beta_basis`, `binned_ref_trans_kry`, `binned_alt_trans_haz`)."""
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import Tensor, nn
 from torch.nn.utils import parametrize
@@ -20,14 +18,14 @@ from torch.nn.utils import parametrize
 from permutect_amd.data.batch import Batch, DownsampledBatch
 from permutect_amd.data.datum import Data
 from permutect_amd.enums import Label, Variation
+# ADAMW_DEFAULTS: with which the balance fit's optimizer is built (reference downsampler.py:143): the device fit's hyperparameters
+from permutect_amd.stats_utils import ADAMW_DEFAULTS, beta_binomial_log_lk, fits_on_device
 
 # reference data/count_binning.py:9-26
 MAX_REF_COUNT, MIN_ALT_COUNT, MAX_ALT_COUNT, COUNT_BIN_SKIP = 10, 1, 15, 3
 NUM_REF_COUNT_BINS = (MAX_REF_COUNT // COUNT_BIN_SKIP) + 1
 NUM_ALT_COUNT_BINS = ((MAX_ALT_COUNT - MIN_ALT_COUNT) // COUNT_BIN_SKIP) + 1
 BETA_BASIS_SHAPES = ((1.0, 1.0), (1.0, 5.0), (5.0, 1.0), (5.0, 5.0))  # reference downsampler.py:27 (the kernels use the same)
-# torch.optim.AdamW's defaults, with which the balance fit's optimizer is built (reference downsampler.py:143): the device fit's hyperparameters
-ADAMW_DEFAULTS = {"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2}
 
 
 def ref_count_bin_indices(counts: Tensor) -> Tensor:
@@ -44,13 +42,6 @@ def flattened_slvra_index(batch: Batch) -> Tensor:
     r = ref_count_bin_indices(batch.get(Data.REF_COUNT).long())
     a = alt_count_bin_indices(batch.get(Data.ALT_COUNT).long())
     return (((s * len(Label) + lab) * len(Variation) + v) * NUM_REF_COUNT_BINS + r) * NUM_ALT_COUNT_BINS + a
-
-
-def beta_binomial_log_lk(n: Tensor, k: Tensor, alpha: Tensor, beta: Tensor) -> Tensor:
-    """log P(k | n, alpha, beta) of the beta-binomial (reference utils/stats_utils.py:28-40)."""
-    comb = torch.lgamma(n + 1) - torch.lgamma(n - k + 1) - torch.lgamma(k + 1)
-    return (comb + torch.lgamma(k + alpha) + torch.lgamma(n - k + beta) + torch.lgamma(alpha + beta)
-            - torch.lgamma(n + alpha + beta) - torch.lgamma(alpha) - torch.lgamma(beta))
 
 
 class _LogWeights(nn.Module):  # the reference's LogWeights parametrization (architecture/parameterizations.py)
@@ -116,7 +107,7 @@ class Downsampler(nn.Module):
         decides where AdamW drifts).  A module on the CPU -- or any module under PMT_DOWNSAMPLER_FIT=torch, or one that is not
         float32 -- runs the torch loop below (a few seconds on the CPU; pinned by tests/golden/downsampler_fit.npz) and returns None."""
         params = self.weights_parameters()
-        if params[0].device.type == "cuda" and params[0].dtype == torch.float32 and os.environ.get("PMT_DOWNSAMPLER_FIT", "") != "torch":
+        if fits_on_device(params[0], "PMT_DOWNSAMPLER_FIT"):
             return self._fit_on_device(counts_slvra, steps)
         for p in params:
             p.requires_grad_(True)

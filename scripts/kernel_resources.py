@@ -13,7 +13,7 @@ def main():
     obj, filt = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else ".")
     with tempfile.TemporaryDirectory() as tmp:
         co, fb = tmp + "/dev.co", tmp + "/fatbin"
-        subprocess.run([LLVM + "llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj], check=True)
+        subprocess.run([LLVM + "llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj, tmp + "/copy.o"], check=True)  # (no output file: rewrites obj in place, and make relinks)
         obj = fb
         for target in ("hipv4-amdgcn-amd-amdhsa--gfx950", "hip-amdgcn-amd-amdhsa--gfx950"):
             r = subprocess.run([LLVM + "clang-offload-bundler", "--type=o", f"--targets={target}", f"--input={obj}", f"--output={co}", "--unbundle"],

@@ -26,7 +26,7 @@ CPU = torch.device("cpu")
 
 # ---- the kernel's formulas in numpy ----------------------------------------------------------------------------------------------
 def digamma_series(x, dtype=np.float64):
-    """csrc/pmt_spectra_fit.hip: sf_digamma.  psi(x) = psi(x + 1) - 1 / x up to x >= 6 (at most six times), then
+    """csrc/pmt_stats_device.hpp: fit_digamma.  psi(x) = psi(x + 1) - 1 / x up to x >= 6 (at most six times), then
     ln x - 1/(2x) - 1/(12x^2) + 1/(120x^4) - 1/(252x^6) + 1/(240x^8), every operation in `dtype`."""
     one = dtype(1)
     x = np.array(x, dtype=dtype, copy=True)
