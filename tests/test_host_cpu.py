@@ -423,6 +423,34 @@ def test_no_mfma_accumulates_onto_another_opcodes_result_without_wait_states():
     assert found == [], found[:5]
 
 
+def _mfma_chain_checker():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("check_mfma_chains", os.path.join(ROOT, "scripts", "check_mfma_chains.py"))
+    chk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(chk)
+    return chk
+
+
+def _kernel_symbols(path, pattern):
+    """the demangled kernel symbols matching `pattern` in the symbol tables of a library's gfx950 code objects, in the form of the instance
+    tables (tests/test_cnn_instances_gpu.py: kernel_name)"""
+    import subprocess
+    import tempfile
+    from tests.test_cnn_instances_gpu import kernel_name
+    chk = _mfma_chain_checker()
+    found = set()
+    with tempfile.TemporaryDirectory() as tmp:
+        objects = chk.code_objects(path, tmp)
+        assert objects, path
+        for co in objects:
+            table = subprocess.run([chk.LLVM + "llvm-readelf", "--symbols", "--wide", "--demangle", co], capture_output=True, text=True, check=True).stdout
+            for line in table.splitlines():
+                cols = line.split(None, 7)  # Num Value Size Type Bind Vis Ndx Name
+                if len(cols) == 8 and cols[3] == "FUNC" and re.search(pattern, cols[7]):
+                    found.add(kernel_name(cols[7]))
+    return found
+
+
 def test_every_cnn_kernel_instance_is_claimed_by_a_test_row():
     """tests/test_cnn_instances_gpu.py runs every compiled instance of the haplotype-CNN kernels at the edges of its scheduling rule; its
     table says which row reaches which kernel symbol.  Here the table is held against the build: the demangled `pmt_cnn*_kernel` symbols
@@ -430,26 +458,10 @@ def test_every_cnn_kernel_instance_is_claimed_by_a_test_row():
     without a test row fails here, and so does a row that claims a symbol nobody compiled); the other libraries (wide builds, per-shape
     instances) may carry no CNN kernel the table does not know."""
     import glob
-    import importlib.util
-    import subprocess
-    import tempfile
     from tests.test_cnn_instances_gpu import ROWS, claimed_kernels, kernel_name
-    spec = importlib.util.spec_from_file_location("check_mfma_chains", os.path.join(ROOT, "scripts", "check_mfma_chains.py"))
-    chk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(chk)
 
     def cnn_kernels(path):
-        found = set()
-        with tempfile.TemporaryDirectory() as tmp:
-            objects = chk.code_objects(path, tmp)
-            assert objects, path
-            for co in objects:
-                table = subprocess.run([chk.LLVM + "llvm-readelf", "--symbols", "--wide", "--demangle", co], capture_output=True, text=True, check=True).stdout
-                for line in table.splitlines():
-                    cols = line.split(None, 7)  # Num Value Size Type Bind Vis Ndx Name
-                    if len(cols) == 8 and cols[3] == "FUNC" and re.search(r"\bpmt_cnn\d*_\w+_kernel\b", cols[7]):
-                        found.add(kernel_name(cols[7]))
-        return found
+        return _kernel_symbols(path, r"\bpmt_cnn\d*_\w+_kernel\b")
 
     assert kernel_name("void pmt_cnn2_forward_kernel<2>(PmtModel const*, float const*)") == "pmt_cnn2_forward_kernel<2>"
     assert kernel_name("pmt_cnn_forward_kernel.kd") == "pmt_cnn_forward_kernel"
@@ -501,3 +513,82 @@ def test_instance_libraries_carry_the_default_librarys_build_id(tmp_path, monkey
         warnings.simplefilter("always")
         lib = I.library_for(desc)
     assert lib is L.load() and any("OTHER sources" in str(w.message) for w in caught), [str(w.message)[:80] for w in caught]
+
+
+def test_every_rows_kernel_instance_is_claimed_by_a_test_row():
+    """The twin of the CNN test above for tests/test_rows_instances_gpu.py: the demangled `pmt_rows_*_kernel` symbols of the default library's
+    gfx950 code objects must EQUAL what the table's default-library rows claim (eight forward instances, two backward instances, the fold);
+    the other libraries (wide builds: NT = 8; per-shape instances) may carry no row kernel that no row of the table claims.  It reads symbol
+    tables, and the kernel names one traced run of the table left in profiles/rows_instances_kernel_names.txt."""
+    import glob
+    from tests.test_cnn_instances_gpu import kernel_name
+    from tests.test_rows_instances_gpu import ROWS, claimed_kernels
+
+    def rows_kernels(path):
+        return _kernel_symbols(path, r"\bpmt_rows_\w+_kernel\b")
+
+    assert kernel_name("void pmt_rows_forward_kernel<true, false, 4>(PmtModel const*, int)") == "pmt_rows_forward_kernel<true, false, 4>"
+    assert len({row.id for row in ROWS}) == len(ROWS)
+    claimed = claimed_kernels(wide_lib=False)
+    default = rows_kernels(os.path.join(ROOT, "permutect_amd", "libpermutect_amd.so"))
+    assert len(default) == 11, sorted(default)  # 2 x 2 x 2 forward, 2 backward, the fold
+    assert default - claimed == set(), f"compiled, but no row of tests/test_rows_instances_gpu.py runs it: {sorted(default - claimed)}"
+    assert claimed - default == set(), f"claimed by a row, but not in the library: {sorted(claimed - default)}"
+    wide = rows_kernels(os.path.join(ROOT, "permutect_amd", "libpermutect_amd_wide.so"))
+    assert claimed_kernels(wide_lib=True) - wide == set(), sorted(claimed_kernels(wide_lib=True) - wide)
+    others = sorted(set(glob.glob(os.path.join(ROOT, "permutect_amd", "*.so")) + glob.glob(os.path.join(ROOT, "permutect_amd", "instances", "*.so")))
+                    - {os.path.join(ROOT, "permutect_amd", "libpermutect_amd.so")})
+    assert len(others) >= 4, others
+    for path in others:
+        extra = rows_kernels(path) - claimed_kernels()
+        assert extra == set(), (path, sorted(extra))
+    # the kernel trace of one run of the table on the GPU (rocprofv3 --kernel-trace --stats): every claimed kernel, the wide build's included
+    with open(os.path.join(ROOT, "profiles", "rows_instances_kernel_names.txt")) as f:
+        traced = {kernel_name(line) for line in f if line.strip() and not line.startswith("#")}
+    assert traced == claimed_kernels(), (sorted(traced - claimed_kernels()), sorted(claimed_kernels() - traced))
+
+
+def test_the_row_kernel_tables_reference_side_works_on_every_row(monkeypatch):
+    """tests/test_rows_instances_gpu.py before it meets a GPU: every table row is lowered on the CPU and lands on the instance it claims (the
+    restated host arithmetic and pmt_rows_workspace_floats are host code), the lists beyond the kernel limits are refused, and its oracle --
+    `O.mlp` in float64 and float32 on 300 seeded rows, the dropout rows with a seeded stand-in mask -- gives a finite yardstick below 1e-4
+    and a nonzero reference gradient for every one-hot probe."""
+    from permutect_amd.engine.plan import EnginePlan, ParamSpace
+    from tests import test_rows_instances_gpu as T
+    monkeypatch.delenv("PMT_LIB", raising=False)
+    for row in T.ROWS:
+        model, named, sd = T.build_model(row, monkeypatch, CPU)
+        space = ParamSpace(model, CPU)
+        if row.wide_lib:
+            with pytest.warns(UserWarning, match="WIDE build"):
+                plan = EnginePlan(model, space, CPU)
+        else:
+            plan = EnginePlan(model, space, CPU)
+        T.assert_instance(row, plan.desc, plan.lib, space, [p for _, p in named])
+        orc = T.Oracle(row, sd, T.stand_in_masks(row.dropout) if row.dropout else None)
+        assert orc.n_max == (65537 if row.big else 4097) and list(sd) == [k for k in model.state_dict() if k.startswith(T.PREFIX[row.which] + ".")]
+        ref = orc.upto(300)
+        assert ref["fwd"].shape == (300, orc.out_dim) and ref["din"].shape == (300, row.in_dim)
+        yard = T.rel_l2(ref["g32"], ref["g"])
+        assert np.isfinite(yard) and 0 < yard < 1e-4, (row.id, yard)
+        assert np.all(np.isfinite(ref["g"])) and np.abs(ref["din"]).max() > 0 and np.abs(ref["fwd32"] - ref["fwd"]).max() < T.FWD_TOL
+        assert T.probes(300) == [0, 256, 288, 299]
+        for v in T.probes(300):
+            r64, r32, din64, din32 = orc.one(v)
+            assert np.all(np.isfinite(r64)) and np.linalg.norm(r64) > 0 and np.linalg.norm(din64) > 0, (row.id, v)
+            assert T.rel_l2(r32, r64) < 1e-4, (row.id, v)
+            assert T.rel_l2(din64, ref["din"][v]) < 1e-12, (row.id, v)  # a row's d_in does not depend on its batch
+        # the chunked running sum is the sum of its rows (with dropout: the masks are a function of the row, not of the chunk)
+        three = T.Oracle(row, sd, orc.masks)
+        assert T.rel_l2(three.upto(3)["g"], sum(three.one(v)[0] for v in range(3))) < 1e-12, row.id
+        assert T.rel_l2(three.upto(7)["g"], three.upto(3)["g"] + sum(three.one(v)[0] for v in range(3, 7))) < 1e-12, row.id
+        if row.dropout:  # the masks bite (all-ones masks: the Dropout modules still shift the state_dict's indices)
+            kept = T.Oracle(row, sd, lambda key, y, row0=0: torch.ones(tuple(y.shape)))
+            assert np.abs(kept.upto(300)["fwd"] - ref["fwd"]).max() > 1e-3
+    assert T.probes(1) == [0] and T.probes(17) == [0, 16] and T.probes(4097) == [0, 4096] and T.probes(65537) == [0, 65536]
+    assert T.probes(65536) == [0, 65280, 65504, 65520, 65535]
+    assert sorted(T.row_counts(T.ROWS[0]))[-2:] == [65536, 65537] and max(T.row_counts(T.ROWS[2])) == 4097
+    for name, in_dim, layers, message in T.REFUSED:
+        model, _ = T.make_model(T.INFO, in_dim, layers, CPU)
+        with pytest.raises(L.PmtError, match=message):
+            EnginePlan(model, ParamSpace(model, CPU), CPU)
