@@ -148,6 +148,14 @@ typedef struct PmtHead {
 #define PMT_CNN_SELU 3
 #define PMT_CNN_FLATTEN 4
 #define PMT_CNN_LINEAR 5
+#define PMT_CNN_BATCHNORM 6     /* BatchNorm1d on BATCH statistics: only in the training descriptor handed to pmt_cnn_bn_forward / _backward
+                                   (PmtModel.cnn never holds one: there the BatchNorms are folded into their neighbours, eval mode).
+                                   in_ch / in_len = out_ch / out_len (behind a flatten: in_ch = C * L, in_len = 1, every flattened feature
+                                   its own channel); w_src / b_src = theta offsets of weight / bias; a region of its own
+                                   (out_off != in_off); reserved[0] = offset of its PMT_CNN_BN_STATS * in_ch floats in the statistics buffer */
+#define PMT_CNN_BN_STATS 5      /* per BatchNorm channel c of C, at reserved[0] + k * C + c: k = 0 batch mean, 1 rstd = 1 / sqrt(biased variance + eps),
+                                   2 unbiased variance (forward); 3 mean of dy, 4 mean of dy * xhat (backward) */
+#define PMT_CNN_BN_EPS 1e-5f    /* torch.nn.BatchNorm1d's default */
 typedef struct PmtCnnLayer {
     int32_t kind;
     int32_t in_ch, in_len, out_ch, out_len;     /* LINEAR (after FLATTEN): in_ch = features, in_len = out_len = 1 */
@@ -165,7 +173,7 @@ typedef struct PmtCnn {
     int32_t out_dim;    /* width of the haplotype embedding */
     int32_t max_act;    /* max floats of any single activation (including the 10*S input) */
     int32_t sum_act;    /* floats of input + every layer output (backward keeps them all in LDS) */
-    int32_t reserved[3];
+    int32_t reserved[3];  /* training descriptor: [0] = floats of the statistics buffer */
     PmtCnnLayer layers[PMT_MAX_CNN_LAYERS];
 } PmtCnn;
 
@@ -775,6 +783,26 @@ int pmt_cnn_backward(const PmtModel* model_host, const PmtModel* model_dev, cons
                      const float* stash, float* grad_theta, float* workspace, size_t workspace_floats, void* stream);
 /* Floats of workspace pmt_cnn_backward can use for this model on the current device (0: its kernels for this model use atomics). */
 size_t pmt_cnn_workspace_floats(const PmtModel* model_host);
+
+/* The haplotype CNN with its `batch_norm` tokens on BATCH statistics (torch.nn.BatchNorm1d in train mode: eps 1e-5, affine), forward and
+ * backward.  `cnn_host` / `cnn_dev`: the TRAINING descriptor -- the stack of model->cnn with its PMT_CNN_BATCHNORM layers kept, the
+ * convolutions carrying the same PmtLinear ids -- on the host and a copy of it in device memory; theta / packed are the UNFOLDED
+ * parameters.  The statistics of BatchNorm k depend on those of every BatchNorm in front of it, so one call makes 2 K + 1 launches on
+ * `stream` for K BatchNorms (per BatchNorm a pass that writes per-workgroup partial sums and a fold of them in fp64 in a fixed order, then
+ * the full pass): no host synchronisation, no grid barrier, no float atomics in the statistics -- they are the same bits on every call.
+ * `stats`: device, cnn_host->reserved[0] floats (PMT_CNN_BN_STATS per channel); written by the forward, read and completed by the backward
+ * of the same haplotypes and weights.  `workspace`: device, >= pmt_cnn_bn_workspace_floats(cnn_host, n) floats, contents irrelevant.
+ * The backward recomputes the forward in LDS and ADDS every parameter gradient (the BatchNorms' weight / bias included) to grad_theta.
+ * PMT_E_INVALID when a BatchNorm would see a single value per channel (n = 1 in front of a length-1 layer: torch raises ValueError),
+ * PMT_E_UNSUPPORTED when not even one variant fits the LDS budget. */
+int pmt_cnn_bn_forward(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                       const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n, float* out,
+                       int64_t out_stride, float* stats, float* workspace, size_t workspace_floats, void* stream);
+int pmt_cnn_bn_backward(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                        const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                        const float* d_out, int64_t d_out_stride, float* stats, float* grad_theta, float* workspace,
+                        size_t workspace_floats, void* stream);
+size_t pmt_cnn_bn_workspace_floats(const PmtCnn* cnn_host, int32_t n);
 
 /* Global-norm clip + AdamW over the flat parameter buffer, one launch sequence, no host sync.
  * Replaces nn.utils.clip_grad_norm_(max_norm=1.0) + torch.optim.AdamW.step (reference misc_utils.py:128-129).

@@ -168,17 +168,45 @@ class ArtifactModel(nn.Module):
             flag = self.__dict__["_cnn_bn_flag"] = any(isinstance(m, nn.BatchNorm1d) for m in self.haplotypes_cnn.modules())
         return flag
 
+    def train_cnn_batch_norm(self, enabled: bool = True):
+        """Train the haplotype CNN's `batch_norm` tokens (reference dna_sequence_convolution.py:82-83) on BATCH statistics, as torch's
+        BatchNorm1d does in train mode: once enabled, every forward with `self.training` true -- grad mode or not -- normalises with the
+        statistics of the batch and updates the running statistics (pmt_cnn_bn_forward / _backward); a forward in eval mode runs the
+        folded eval-mode stack as before.  Plain Python state: not in state_dict, not in the checkpoint; train_artifact_model switches it
+        on for a CNN that holds a BatchNorm1d.  The statistics are those of THIS process's batch: with a process group of more than one
+        rank the replicas would normalise differently, and synchronised statistics are not built -- refused."""
+        if enabled:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise L.PmtError(f"train_cnn_batch_norm: batch statistics across the {dist.get_world_size()} ranks of a process group are not "
+                                 "built (every replica would normalise with its own batch's statistics); train a haplotype CNN with "
+                                 "batch_norm tokens in a single process")
+            n_layers = len(list(self.haplotypes_cnn._model.children()))
+            if n_layers > L.MAX_CNN_LAYERS:
+                raise L.PmtError(f"train_cnn_batch_norm: the haplotype CNN has {n_layers} layers with its batch_norm tokens counted, the "
+                                 f"training kernels take {L.MAX_CNN_LAYERS} (the eval-mode stack, BatchNorms folded away, is not affected)")
+        self.__dict__["_cnn_bn_train"] = bool(enabled)
+        return self
+
     def _encode(self, batch: Batch):
+        cnn_batch_stats = False
         if self.training and self._cnn_has_batchnorm():
-            # the reference's `batch_norm` token of the haplotype CNN (dna_sequence_convolution.py:82-83): same story as below
-            raise NotImplementedError("permutect_amd runs a haplotype CNN with batch_norm tokens in eval mode only (model.eval() under "
-                                      "no_grad / inference_mode: filter_variants, evaluation); training with BatchNorm statistics is not built")
+            # the reference's `batch_norm` token of the haplotype CNN (dna_sequence_convolution.py:82-83): on batch statistics for a model
+            # that asked for it (train_cnn_batch_norm); otherwise the same story as below
+            if not self.__dict__.get("_cnn_bn_train", False):
+                raise NotImplementedError("permutect_amd runs a haplotype CNN with batch_norm tokens in eval mode only (model.eval() under "
+                                          "no_grad / inference_mode: filter_variants, evaluation) unless training on batch statistics is "
+                                          "switched on.  ArtifactModel.train_cnn_batch_norm() switches it on.")
+            cnn_batch_stats = True
         if self.training and self._params.batch_normalize:
             # reference mlp.py:52-53: BatchNorm1d normalises with the statistics of the whole batch in train mode.  The kernels run its
             # eval-mode form (running statistics folded into the Linear behind it, engine/plan.py): refuse, never train on the wrong map.
             raise NotImplementedError("permutect_amd runs a batch_normalize model in eval mode only (model.eval(): filter_variants, "
                                       "evaluation); training with BatchNorm statistics is not built")
         eng = self.engine()
+        eng.cnn_batch_stats = cnn_batch_stats
+        if cnn_batch_stats:
+            eng.plan.cnn_train_desc(self)  # (lowered once)
         # reference mlp.py:57-58: nn.Dropout draws new masks on every forward in train mode and is the identity in eval mode
         eng.draw_dropout_seed(self.training)
         if batch.size() == 0:  # nothing to launch

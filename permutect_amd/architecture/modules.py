@@ -279,9 +279,9 @@ class DNASequenceConvolution(nn.Module):
             elif kind == "selu":
                 layers.append(nn.SELU())
             elif kind == "batch_norm":
-                # reference dna_sequence_convolution.py:82-83.  The kernels have no such layer: in eval mode the engine folds its
-                # per-channel affine map into the convolution / linear next to it (engine/plan.py: _lower_cnn, cnn_bn_folds); training
-                # with batch statistics is refused (ArtifactModel.compute_batch_output)
+                # reference dna_sequence_convolution.py:82-83.  In eval mode the engine folds its per-channel affine map into the
+                # convolution / linear next to it (engine/plan.py: _lower_cnn, cnn_bn_folds); training on batch statistics runs
+                # kernels of its own (csrc/pmt_cnn_bn.hip) for a model that asked for it (ArtifactModel.train_cnn_batch_norm)
                 layers.append(nn.BatchNorm1d(channels))
             elif kind == "flatten":
                 layers.append(nn.Flatten())

@@ -66,7 +66,8 @@ class PmtHead(C.Structure):
 
 
 MAX_CNN_LAYERS = 12
-CNN_CONV, CNN_POOL, CNN_LEAKY_RELU, CNN_SELU, CNN_FLATTEN, CNN_LINEAR = range(6)
+CNN_CONV, CNN_POOL, CNN_LEAKY_RELU, CNN_SELU, CNN_FLATTEN, CNN_LINEAR, CNN_BATCHNORM = range(7)
+CNN_BN_STATS = 5  # floats per BatchNorm channel in the statistics buffer of pmt_cnn_bn_forward / _backward (PMT_CNN_BN_STATS)
 
 
 class PmtCnnLayer(C.Structure):
@@ -205,6 +206,7 @@ class PmtPosteriorParams(C.Structure):
 EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", "pmt_limits", "pmt_struct_bytes", "pmt_model_check", "pmt_plan_groups", "pmt_plan_groups_device", "pmt_plan_device_chunks", "pmt_stash_bytes", "pmt_pack_params",
            "pmt_scan_counts", "pmt_forward", "pmt_backward", "pmt_clip_adamw",
            "pmt_dropout_mask", "pmt_rows_stash_bytes", "pmt_rows_forward", "pmt_rows_backward", "pmt_rows_workspace_floats", "pmt_cnn_forward", "pmt_cnn_backward", "pmt_cnn_stash_floats", "pmt_cnn_workspace_floats",
+           "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
            "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_update", "pmt_record_losses", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
@@ -255,6 +257,10 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_cnn_workspace_floats.argtypes = [P(PmtModel)]
     lib.pmt_cnn_workspace_floats.restype = C.c_size_t
     lib.pmt_cnn_stash_floats.argtypes = [P(PmtModel)]
+    lib.pmt_cnn_bn_forward.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, C.c_size_t, vp]
+    lib.pmt_cnn_bn_backward.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, C.c_size_t, vp]
+    lib.pmt_cnn_bn_workspace_floats.argtypes = [P(PmtCnn), i32]
+    lib.pmt_cnn_bn_workspace_floats.restype = C.c_size_t
     lib.pmt_cnn_stash_floats.restype = C.c_size_t
     lib.pmt_rows_stash_bytes.argtypes = [P(PmtModel), i32, i32]
     lib.pmt_rows_stash_bytes.restype = C.c_size_t
@@ -298,7 +304,7 @@ def load(path: str = None) -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("pmt_abi_version", "pmt_stash_bytes", "pmt_rows_stash_bytes", "pmt_layered_scratch_floats",
                         "pmt_layered_backward_scratch_floats", "pmt_cnn_stash_floats", "pmt_cnn_workspace_floats",
-                        "pmt_rows_workspace_floats"):
+                        "pmt_rows_workspace_floats", "pmt_cnn_bn_workspace_floats"):
             fn.restype = i32
     lib.pmt_struct_bytes.argtypes = [i32]
     if lib.pmt_abi_version() != ABI_VERSION:

@@ -406,7 +406,8 @@ class EnginePlan:
           "out": directly behind a Conv1d / Linear -> that layer's output rows:   W' = diag(s) W,  b' = s b + t;
           "in":  otherwise in front of (a Flatten and) an un-padded Conv1d / a Linear -> its input channels:  W' = W diag(s),
                  b' = b + W t  (a zero-padded convolution would see t only inside the sequence: refused).
-        Returns the layer list without the BatchNorms.  Training with batch statistics is refused by ArtifactModel."""
+        Returns the layer list without the BatchNorms.  Training on batch statistics runs another descriptor with the BatchNorms kept
+        (cnn_train_desc), and only for a model that asked for it (ArtifactModel.train_cnn_batch_norm)."""
         kept = []
         for i, layer in enumerate(layers):
             if not isinstance(layer, nn.BatchNorm1d):
@@ -428,6 +429,57 @@ class EnginePlan:
                 raise L.PmtError("a batch_norm token of the haplotype CNN that is neither directly behind a convolution / linear nor in "
                                  "front of an un-padded convolution / a linear cannot be folded (permutect_amd runs it in eval mode only)")
         return kept
+
+    def cnn_train_desc(self, model) -> L.PmtCnn:
+        """The TRAINING descriptor of the haplotype CNN (pmt_cnn_bn_forward / _backward; ArtifactModel.train_cnn_batch_norm): the stack of
+        `desc.cnn` with its BatchNorm1d layers kept as PMT_CNN_BATCHNORM layers -- a region of their own, the theta offsets of their weight
+        / bias, an offset into the per-call statistics buffer -- and the convolutions carrying the PmtLinear ids they have in `desc.cnn`.
+        Lowered on first use; `desc.cnn` and everything that runs it stay as they are."""
+        if getattr(self, "_cnn_train", None) is not None:
+            return self._cnn_train
+        assert model is not None, "lowered at the opt-in (ArtifactModel._encode) before any kernel call asks for it"
+        layers = list(model.haplotypes_cnn._model.children())
+        if len(layers) > L.MAX_CNN_LAYERS:
+            raise L.PmtError(f"haplotype CNN with {len(layers)} layers (its batch_norm tokens counted) exceeds the kernel limit {L.MAX_CNN_LAYERS}")
+        src = self.desc.cnn
+        eval_layers = iter([src.layers[i] for i in range(src.n_layers)])
+        dst = L.PmtCnn()
+        ch, length = M.INITIAL_NUM_CHANNELS, src.seq_len
+        off, in_off, max_act, stats_off = ch * length, 0, ch * length, 0
+        self.cnn_train_bns = []  # (BatchNorm1d, offset in the statistics buffer), stack order
+        for i, layer in enumerate(layers):
+            c = dst.layers[i]
+            if isinstance(layer, nn.BatchNorm1d):
+                if layer.num_features != ch or not layer.affine or not layer.track_running_stats or layer.momentum is None:
+                    raise L.PmtError("unsupported BatchNorm1d options in the haplotype CNN")
+                c.kind, c.in_ch, c.in_len, c.out_ch, c.out_len = L.CNN_BATCHNORM, ch, length, ch, length
+                c.kernel, c.stride, c.padding, c.dilation, c.lin = 1, 1, 0, 1, -1
+                c.w_src, c.b_src = self.space.offset_of(layer.weight), self.space.offset_of(layer.bias)
+                c.in_off, c.out_off = in_off, off
+                c.reserved[0] = stats_off
+                self.cnn_train_bns.append((layer, stats_off))
+                stats_off += L.CNN_BN_STATS * ch
+                in_off = off
+                off += ch * length
+                continue
+            e = next(eval_layers)  # the same layer of the eval-mode stack: its geometry, other regions
+            for name, _ in L.PmtCnnLayer._fields_:
+                if name != "reserved":
+                    setattr(c, name, getattr(e, name))
+            assert (c.in_ch, c.in_len) == (ch, length), "the training stack follows the eval-mode stack"
+            c.in_off = in_off
+            if c.kind in (L.CNN_LEAKY_RELU, L.CNN_SELU, L.CNN_FLATTEN):  # in place / a view
+                c.out_off = in_off
+            else:
+                c.out_off = in_off = off
+                off += c.out_ch * c.out_len
+            ch, length = c.out_ch, c.out_len
+            max_act = max(max_act, ch * length)
+        dst.n_layers, dst.seq_len, dst.out_dim, dst.max_act, dst.sum_act = len(layers), src.seq_len, ch * length, max_act, off
+        dst.reserved[0] = stats_off
+        self._cnn_train = dst
+        self.cnn_train_dev = torch.frombuffer(bytearray(bytes(dst)), dtype=torch.uint8).to(self.device)
+        return dst
 
     def folded_cnn_theta(self, theta: torch.Tensor) -> torch.Tensor:
         """A copy of the flat parameter buffer in which the haplotype CNN's convolutions / linear carry their folded BatchNorms

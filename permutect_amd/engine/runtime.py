@@ -28,6 +28,11 @@ def _stream() -> int:
     return L.raw_stream()
 
 
+_CNN_BN_REFUSAL = ("a haplotype CNN with batch_norm tokens runs under no_grad / inference_mode only (its BatchNorms are folded into the "
+                   "neighbouring layers' weights) unless training on batch statistics is switched on.  "
+                   "ArtifactModel.train_cnn_batch_norm() switches it on.")
+
+
 class ReadSetEngine:
     def __init__(self, model, device: torch.device):
         if device.type != "cuda":
@@ -50,6 +55,9 @@ class ReadSetEngine:
         # (the fused optimizer kernel, a captured-graph replay, a collective on the flat buffer)
         self.join_layered = os.environ.get("PMT_LAYERED_JOIN", "1") != "0"
         self.dropout_seed = 0  # this step's dropout masks (draw_dropout_seed; 0 = none)
+        # this call runs the haplotype CNN's BatchNorms on BATCH statistics (set by ArtifactModel._encode on every forward: train mode of a
+        # model that opted in, ArtifactModel.train_cnn_batch_norm; plan.cnn_train_desc has been lowered by then)
+        self.cnn_batch_stats = False
         # ONE persistent fault word for every joined launch of this engine (PmtBatch.join_fault): a launch whose bounded wait for
         # another workgroup gave up stores 1 there and its numbers are wrong.  Read by check_join_fault() wherever the callers
         # synchronise anyway: end of a training / evaluation epoch, end of a filtering pass, bench.py, the tests.
@@ -130,6 +138,51 @@ class ReadSetEngine:
                                              packed_f.data_ptr(), _stream()), "pmt_pack_params")
             self._cnn_fold, self._cnn_fold_key = (theta_f, packed_f), key
         return self._cnn_fold
+
+    def cnn_bn_forward(self, hap: Tensor, out_ptr: int, out_stride: int) -> Tensor:
+        """The haplotype CNN on batch statistics (pmt_cnn_bn_forward: 2 K + 1 launches for K BatchNorms) into the rows at `out_ptr`, then the
+        running statistics of every BatchNorm as torch updates them in train mode (running <- (1 - momentum) running + momentum batch, the
+        UNBIASED batch variance; num_batches_tracked += 1): two more launches, no host synchronisation.  Returns the statistics buffer,
+        which the backward of the same call reads and completes."""
+        plan, n = self.plan, hap.shape[0]
+        c = plan.cnn_train_desc(None)
+        for layer, (bn, _) in zip([c.layers[i] for i in range(c.n_layers) if c.layers[i].kind == L.CNN_BATCHNORM], plan.cnn_train_bns):
+            if n * layer.in_len < 2:  # torch.nn.functional.batch_norm in train mode
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size [{n}, {layer.in_ch}"
+                                 + (f", {layer.in_len}]" if layer.in_len > 1 else "]"))
+        stats = torch.empty(max(c.reserved[0], 4), dtype=torch.float32, device=self.device)
+        ws = torch.empty(max(self.lib.pmt_cnn_bn_workspace_floats(C.byref(c), n), 4), dtype=torch.float32, device=self.device)
+        L.check(self.lib.pmt_cnn_bn_forward(C.byref(plan.desc), plan.desc_dev.data_ptr(), C.byref(c), plan.cnn_train_dev.data_ptr(),
+                                            self.space.theta.data_ptr(), plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, out_ptr,
+                                            out_stride, stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "pmt_cnn_bn_forward")
+        with torch.no_grad():
+            running, batch = [], []
+            for bn, off in plan.cnn_train_bns:
+                nc = bn.num_features
+                running += [bn.running_mean, bn.running_var]
+                batch += [stats[off:off + nc], stats[off + 2 * nc:off + 3 * nc]]
+            momenta = {float(bn.momentum) for bn, _ in plan.cnn_train_bns}
+            if len(momenta) == 1:
+                torch._foreach_lerp_(running, batch, momenta.pop())
+            else:
+                for i, (bn, _) in enumerate(plan.cnn_train_bns):
+                    torch._foreach_lerp_(running[2 * i:2 * i + 2], batch[2 * i:2 * i + 2], float(bn.momentum))
+            torch._foreach_add_([bn.num_batches_tracked for bn, _ in plan.cnn_train_bns], 1)
+        # the eval-mode fold (cnn_params) is a function of these buffers: dropped by hand -- the fused _foreach kernels write them without
+        # moving their version counters, which is all params_key() sees of them
+        self._cnn_fold_key = None
+        return stats
+
+    def cnn_bn_backward(self, hap: Tensor, d_out_ptr: int, d_out_stride: int, stats: Tensor):
+        """pmt_cnn_bn_backward: recomputes the forward from `stats` (the running statistics are not touched again) and adds every gradient
+        of the haplotype CNN, its BatchNorms' weight / bias included, to the flat gradient buffer"""
+        plan, n = self.plan, hap.shape[0]
+        c = plan.cnn_train_desc(None)
+        ws = torch.empty(max(self.lib.pmt_cnn_bn_workspace_floats(C.byref(c), n), 4), dtype=torch.float32, device=self.device)
+        L.check(self.lib.pmt_cnn_bn_backward(C.byref(plan.desc), plan.desc_dev.data_ptr(), C.byref(c), plan.cnn_train_dev.data_ptr(),
+                                             self.space.theta.data_ptr(), plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, d_out_ptr,
+                                             d_out_stride, stats.data_ptr(), self.space.gtheta.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _stream()), "pmt_cnn_bn_backward")
 
     def cnn_workspace(self) -> Optional[Tensor]:
         """private rows for the haplotype CNN's weight-gradient sums (pmt_cnn_backward: workspace); PMT_CNN_WORKSPACE=0: atomics"""
@@ -386,14 +439,18 @@ class HaplotypeCnnFunction(torch.autograd.Function):
         # (PMT_CNN_STASH=0: let the backward recompute the layer outputs instead; the parity tests cover both)
         per = engine.lib.pmt_cnn_stash_floats(C.byref(d)) if train and os.environ.get("PMT_CNN_STASH", "1") != "0" else 0
         stash = torch.empty(n * per, dtype=torch.float32, device=engine.device) if per > 0 and n > 0 else None
-        if train and engine.plan.cnn_bn_folds:
-            raise NotImplementedError("a haplotype CNN with batch_norm tokens runs under no_grad / inference_mode only (its BatchNorms are folded "
-                                      "into the neighbouring layers' weights); a backward through it is not built")
-        cnn_theta, cnn_packed = engine.cnn_params()
-        L.check(engine.lib.pmt_cnn_forward(C.byref(d), engine.plan.desc_dev.data_ptr(), cnn_theta.data_ptr(),
-                                           cnn_packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, out.data_ptr(), out.stride(0),
-                                           _ptr(stash), _stream()),
-                "pmt_cnn_forward")
+        ctx.bn_stats = None
+        if engine.cnn_batch_stats and n > 0:  # the BatchNorms on batch statistics: kernels of their own, no stash
+            stash = None
+            ctx.bn_stats = engine.cnn_bn_forward(hap, out.data_ptr(), out.stride(0))
+        else:
+            if train and engine.plan.cnn_bn_folds:
+                raise NotImplementedError(_CNN_BN_REFUSAL)
+            cnn_theta, cnn_packed = engine.cnn_params()
+            L.check(engine.lib.pmt_cnn_forward(C.byref(d), engine.plan.desc_dev.data_ptr(), cnn_theta.data_ptr(),
+                                               cnn_packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, out.data_ptr(), out.stride(0),
+                                               _ptr(stash), _stream()),
+                    "pmt_cnn_forward")
         ctx.engine, ctx.train, ctx.stash = engine, train, stash
         ctx.hap = hap  # integer tensor: kept on ctx (save_for_backward is for differentiable tensors' bookkeeping)
         return out
@@ -406,6 +463,10 @@ class HaplotypeCnnFunction(torch.autograd.Function):
         eng.space.bind_grads(quick=True)
         if d_out.dtype != torch.float32 or d_out.stride(-1) != 1:
             d_out = d_out.float().contiguous()
+        if ctx.bn_stats is not None:
+            eng.cnn_bn_backward(hap, d_out.data_ptr(), d_out.stride(0), ctx.bn_stats)
+            ctx.bn_stats = None
+            return None, None, None
         ws = eng.cnn_workspace()
         L.check(eng.lib.pmt_cnn_backward(C.byref(d), eng.plan.desc_dev.data_ptr(), eng.space.theta.data_ptr(),
                                          eng.plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), hap.shape[0], d_out.data_ptr(), d_out.stride(0),
@@ -442,13 +503,17 @@ class VariantEmbedFunction(torch.autograd.Function):
         L.check(lib.pmt_rows_forward(C.byref(d), engine.plan.desc_dev.data_ptr(), L.ROWS_INFO, engine.space.theta.data_ptr(),
                                      engine.plan.packed.data_ptr(), x.data_ptr(), x.stride(0), n, ve.data_ptr(), ve.stride(0),
                                      _ptr(rows_stash), engine.dropout_seed, _stream()), "pmt_rows_forward")
-        if train and engine.plan.cnn_bn_folds:
-            raise NotImplementedError("a haplotype CNN with batch_norm tokens runs under no_grad / inference_mode only (its BatchNorms are folded "
-                                      "into the neighbouring layers' weights); a backward through it is not built")
-        cnn_theta, cnn_packed = engine.cnn_params()
-        L.check(lib.pmt_cnn_forward(C.byref(d), engine.plan.desc_dev.data_ptr(), cnn_theta.data_ptr(),
-                                    cnn_packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, ve.data_ptr() + 4 * e_info, ve.stride(0),
-                                    _ptr(cnn_stash), _stream()), "pmt_cnn_forward")
+        ctx.bn_stats = None
+        if engine.cnn_batch_stats and n > 0:  # the BatchNorms on batch statistics: kernels of their own, no stash
+            cnn_stash = None
+            ctx.bn_stats = engine.cnn_bn_forward(hap, ve.data_ptr() + 4 * e_info, ve.stride(0))
+        else:
+            if train and engine.plan.cnn_bn_folds:
+                raise NotImplementedError(_CNN_BN_REFUSAL)
+            cnn_theta, cnn_packed = engine.cnn_params()
+            L.check(lib.pmt_cnn_forward(C.byref(d), engine.plan.desc_dev.data_ptr(), cnn_theta.data_ptr(),
+                                        cnn_packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, ve.data_ptr() + 4 * e_info, ve.stride(0),
+                                        _ptr(cnn_stash), _stream()), "pmt_cnn_forward")
         ctx.engine, ctx.train, ctx.dropout_seed, ctx.e_info = engine, train, engine.dropout_seed, e_info
         ctx.hap, ctx.cnn_stash = hap, cnn_stash
         if train:
@@ -470,6 +535,10 @@ class VariantEmbedFunction(torch.autograd.Function):
                                           eng.plan.packed.data_ptr(), x.data_ptr(), x.stride(0), n, d_ve.data_ptr(), d_ve.stride(0),
                                           rows_stash.data_ptr(), eng.space.gtheta.data_ptr(), None, 0, 1.0, _ptr(ws),
                                           0 if ws is None else ws.numel(), ctx.dropout_seed, _stream()), "pmt_rows_backward")
+        if ctx.bn_stats is not None:
+            eng.cnn_bn_backward(hap, d_ve.data_ptr() + 4 * ctx.e_info, d_ve.stride(0), ctx.bn_stats)
+            ctx.bn_stats = None
+            return None, None, None, None
         cws = eng.cnn_workspace()
         L.check(eng.lib.pmt_cnn_backward(C.byref(d), eng.plan.desc_dev.data_ptr(), eng.space.theta.data_ptr(),
                                          eng.plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, d_ve.data_ptr() + 4 * ctx.e_info,

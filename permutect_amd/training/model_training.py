@@ -56,6 +56,8 @@ class Checkpoint:
         if loss < self.best_loss:
             self.best_loss = loss
             self.state = self.model.engine().space.theta.detach().clone()
+            # (the running statistics of a haplotype CNN trained with batch_norm tokens are buffers outside theta)
+            self.buffers = [b.detach().clone() for b in self.model.haplotypes_cnn.buffers()]
             self.opt_state = self.opt.state_dict()
 
     def should_roll_back(self, loss: float) -> bool:
@@ -66,6 +68,8 @@ class Checkpoint:
             return False
         with torch.no_grad():
             self.model.engine().space.theta.copy_(self.state)
+            for b, saved in zip(self.model.haplotypes_cnn.buffers(), self.buffers):
+                b.copy_(saved)
         self.opt.load_state_dict(self.opt_state)  # moments, step count and learning rate (reference checkpoint.py:29-31)
         return True
 
@@ -126,6 +130,9 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
         else:
             timing_log(f"downsampler fit (torch): {num_sources * 15} cells, {time.perf_counter() - t_fit:.2f} s")
     model.reset_source_predictor(num_sources)
+    if model._cnn_has_batchnorm():
+        # the reference's `batch_norm` token trains on the statistics of the batch (calibration epochs included: they run in train mode)
+        model.train_cnn_batch_norm()
     opt = FusedClipAdamW(model, lr=training_params.learning_rate, weight_decay=training_params.weight_decay)
     scheduler = PlateauScheduler(opt, min_lr=training_params.learning_rate / 100)
     checkpoint = Checkpoint(model, opt)
