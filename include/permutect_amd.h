@@ -792,7 +792,10 @@ size_t pmt_cnn_workspace_floats(const PmtModel* model_host);
  * the full pass): no host synchronisation, no grid barrier, no float atomics in the statistics -- they are the same bits on every call.
  * `stats`: device, cnn_host->reserved[0] floats (PMT_CNN_BN_STATS per channel); written by the forward, read and completed by the backward
  * of the same haplotypes and weights.  `workspace`: device, >= pmt_cnn_bn_workspace_floats(cnn_host, n) floats, contents irrelevant.
- * The backward recomputes the forward in LDS and ADDS every parameter gradient (the BatchNorms' weight / bias included) to grad_theta.
+ * The backward recomputes the forward in LDS and ADDS every parameter gradient (the BatchNorms' weight / bias included) to grad_theta:
+ * its full pass sums the convolutions' and the linear's gradients in a zeroed private row per workgroup inside `workspace` (the span of
+ * those parameters in the flat buffer; the layers' w_src / b_src must be their PmtLinear's) and a fold adds the rows in workgroup order --
+ * a fill and a launch more, and the gradients, like the statistics, are the same bits on every call.
  * PMT_E_INVALID when a BatchNorm would see a single value per channel (n = 1 in front of a length-1 layer: torch raises ValueError),
  * PMT_E_UNSUPPORTED when not even one variant fits the LDS budget. */
 int pmt_cnn_bn_forward(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
@@ -803,6 +806,44 @@ int pmt_cnn_bn_backward(const PmtModel* model_host, const PmtModel* model_dev, c
                         const float* d_out, int64_t d_out_stride, float* stats, float* grad_theta, float* workspace,
                         size_t workspace_floats, void* stream);
 size_t pmt_cnn_bn_workspace_floats(const PmtCnn* cnn_host, int32_t n);
+
+/* The same computation in STEPS, for batch statistics over the union of several processes' batches (data parallel: R ranks, every rank
+ * its own n >= 1 variants).  A collective cannot go between the launches of one call and the library knows nothing of collectives, so
+ * the caller drives, per BatchNorm `layer` (its index in cnn_host->layers) in dependency order -- ascending in the forward, descending in
+ * the backward:
+ *   1. pmt_cnn_bn_forward_moments / _backward_moments: the statistics (sums) pass of that BatchNorm and a fold of THIS rank's
+ *      per-workgroup partials, in fp64 and in the fold's fixed order, into `moments`: double[3][C] in device memory, C = the layer's
+ *      channels.  Row 0: the values this rank saw per channel, n * in_len.  Row 1: forward sum n_i m_i (= the sum of the values),
+ *      backward sum dy.  Row 2: forward the M2 about this rank's OWN mean, backward sum dy xhat.  Two launches.
+ *   2. the caller's exchange: `moments` of every rank, in rank order, as double[ranks][3][C] (with every other slot zero beforehand a SUM
+ *      all-reduce is that gather: x + 0 is exact).
+ *   3. pmt_cnn_bn_merge: one launch, a thread per channel walking the ranks in order, fp64, no atomics -- the same bits on every rank.
+ *      backward == 0:  N = sum cnt_r,  mean = (sum sum_r) / N,  M2 = sum_r [M2_r + cnt_r (sum_r / cnt_r - mean)^2] over ranks with
+ *      cnt_r > 0;  stores mean, rstd = 1 / sqrt(M2 / N + eps), unbiased variance M2 / (N - 1) into `stats` where the one-call form does.
+ *      backward == 1:  c1 = sum_r (sum dy)_r / N, c2 = sum_r (sum dy xhat)_r / N into `stats`, and ONLY slot `rank`'s own sum dy /
+ *      sum dy xhat added to grad_theta at b_src / w_src (the gradient all-reduce sums the ranks afterwards).
+ *      `n`: this rank's variants, for the checks alone.
+ * then pmt_cnn_bn_forward_full / _backward_full: the last launch of the one-call form, given a complete `stats` buffer.
+ * With ranks == 1 the steps give the bits of pmt_cnn_bn_forward / _backward (sum / N is the same expression, the cross term exactly 0).
+ * K BatchNorms: 3 K + 1 launches each way (the backward's full pass: its fill and fold more).  `workspace` as above.  PMT_E_INVALID: n < 1, a `layer` that is no PMT_CNN_BATCHNORM of the
+ * descriptor, rank outside [0, ranks), and ranks == 1 with n * in_len < 2 (a single value per channel has no variance; with more ranks
+ * every rank holds a value and the union holds at least two). */
+int pmt_cnn_bn_forward_moments(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                               const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                               int32_t layer, const float* stats, double* moments, float* workspace, size_t workspace_floats, void* stream);
+int pmt_cnn_bn_backward_moments(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                                const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                                int32_t layer, const float* d_out, int64_t d_out_stride, const float* stats, double* moments,
+                                float* workspace, size_t workspace_floats, void* stream);
+int pmt_cnn_bn_merge(const PmtModel* model_host, const PmtCnn* cnn_host, int32_t layer, int32_t n, const double* moments, int32_t ranks,
+                     int32_t rank, int32_t backward, float* stats, float* grad_theta, void* stream);
+int pmt_cnn_bn_forward_full(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                            const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n, float* out,
+                            int64_t out_stride, const float* stats, void* stream);
+int pmt_cnn_bn_backward_full(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                             const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                             const float* d_out, int64_t d_out_stride, const float* stats, float* grad_theta, float* workspace,
+                             size_t workspace_floats, void* stream);
 
 /* Global-norm clip + AdamW over the flat parameter buffer, one launch sequence, no host sync.
  * Replaces nn.utils.clip_grad_norm_(max_norm=1.0) + torch.optim.AdamW.step (reference misc_utils.py:128-129).

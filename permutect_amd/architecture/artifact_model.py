@@ -168,24 +168,42 @@ class ArtifactModel(nn.Module):
             flag = self.__dict__["_cnn_bn_flag"] = any(isinstance(m, nn.BatchNorm1d) for m in self.haplotypes_cnn.modules())
         return flag
 
-    def train_cnn_batch_norm(self, enabled: bool = True):
+    def train_cnn_batch_norm(self, enabled: bool = True, sync=False):
         """Train the haplotype CNN's `batch_norm` tokens (reference dna_sequence_convolution.py:82-83) on BATCH statistics, as torch's
         BatchNorm1d does in train mode: once enabled, every forward with `self.training` true -- grad mode or not -- normalises with the
         statistics of the batch and updates the running statistics (pmt_cnn_bn_forward / _backward); a forward in eval mode runs the
-        folded eval-mode stack as before.  Plain Python state: not in state_dict, not in the checkpoint; train_artifact_model switches it
-        on for a CNN that holds a BatchNorm1d.  The statistics are those of THIS process's batch: with a process group of more than one
-        rank the replicas would normalise differently, and synchronised statistics are not built -- refused."""
+        folded eval-mode stack as before.  Plain Python state, `sync` included: not in state_dict, not in the checkpoint;
+        train_artifact_model switches it on for a CNN that holds a BatchNorm1d.
+
+        `sync=False`: the statistics are those of THIS process's batch.  With a process group of more than one rank the replicas would
+        normalise differently -- refused.
+        `sync=True` (the default process group) or a ProcessGroup: the statistics of every BatchNorm are those of the UNION of the ranks'
+        batches, merged on the device in rank order (ReadSetEngine.cnn_bn_forward), so that N ranks with batch B are one process with
+        batch N * B and the replicas' running statistics stay bit-identical: K small all-reduces per direction for K BatchNorms.  It
+        needs an initialised process group, and runs through the collectives at world size 1 too (they are identities there: the bits
+        of the unsynchronised path).  The contract: every rank makes the same sequence of train-mode forwards and backwards, each on
+        at least one variant -- a rank that skips one leaves the others waiting in a collective (train_artifact_model equalises the
+        step count; eval-mode passes run no collective)."""
+        group = None
         if enabled:
             import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                raise L.PmtError(f"train_cnn_batch_norm: batch statistics across the {dist.get_world_size()} ranks of a process group are not "
-                                 "built (every replica would normalise with its own batch's statistics); train a haplotype CNN with "
-                                 "batch_norm tokens in a single process")
+            on = dist.is_available() and dist.is_initialized()
+            if sync is not False and sync is not None:
+                if not on:
+                    raise L.PmtError("train_cnn_batch_norm(sync=...): synchronised statistics need an initialised torch.distributed process "
+                                     "group (torch.distributed.init_process_group, or launch the tool under torchrun)")
+                group = None if sync is True else sync
+            elif on and dist.get_world_size() > 1:
+                raise L.PmtError(f"train_cnn_batch_norm: per-process batch statistics across the {dist.get_world_size()} ranks of a process "
+                                 "group are not what data parallel means (every replica would normalise with its own batch's statistics); "
+                                 "train_cnn_batch_norm(sync=True) synchronises them over the ranks")
             n_layers = len(list(self.haplotypes_cnn._model.children()))
             if n_layers > L.MAX_CNN_LAYERS:
                 raise L.PmtError(f"train_cnn_batch_norm: the haplotype CNN has {n_layers} layers with its batch_norm tokens counted, the "
                                  f"training kernels take {L.MAX_CNN_LAYERS} (the eval-mode stack, BatchNorms folded away, is not affected)")
         self.__dict__["_cnn_bn_train"] = bool(enabled)
+        self.__dict__["_cnn_bn_sync"] = bool(enabled) and sync is not False and sync is not None
+        self.__dict__["_cnn_bn_group"] = group
         return self
 
     def _encode(self, batch: Batch):
@@ -205,8 +223,14 @@ class ArtifactModel(nn.Module):
                                       "evaluation); training with BatchNorm statistics is not built")
         eng = self.engine()
         eng.cnn_batch_stats = cnn_batch_stats
+        eng.cnn_bn_sync = cnn_batch_stats and self.__dict__.get("_cnn_bn_sync", False)
+        eng.cnn_bn_group = self.__dict__.get("_cnn_bn_group")
         if cnn_batch_stats:
             eng.plan.cnn_train_desc(self)  # (lowered once)
+        if eng.cnn_bn_sync and batch.size() == 0:
+            # before any launch: its autograd graph would skip the backward's collectives and leave the other ranks waiting
+            raise L.PmtError("synchronised BatchNorm statistics: this rank's batch is empty; every rank takes part in every train-mode "
+                             "forward and backward with at least one variant")
         # reference mlp.py:57-58: nn.Dropout draws new masks on every forward in train mode and is the identity in eval mode
         eng.draw_dropout_seed(self.training)
         if batch.size() == 0:  # nothing to launch

@@ -19,8 +19,14 @@
 //                                  d(weight) += sum dy xhat
 //              then the full pass: a BatchNorm propagates dx = weight rstd (dy - c1 - xhat c2); weight gradients as in pmt_cnn.hip.
 //
-// 2 K + 1 launches each way, no float atomics anywhere in the statistics: they are the same bits on every call.  Every pass recomputes
+// 2 K + 1 launches each way (the backward: a fill and a fold's two launches more -- its full pass sums the weight gradients in private rows per workgroup,
+// folded in workgroup order), no float atomics anywhere in the statistics nor between workgroups: the same bits on every call.  Every pass recomputes
 // what is in front of it; a stash for these kernels is follow-up work.
+//
+// The STEPPED form (pmt_cnn_bn_forward_moments / _backward_moments, pmt_cnn_bn_merge, pmt_cnn_bn_forward_full / _backward_full) is the same
+// computation cut where a caller's collective goes, for statistics over the union of several ranks' batches: the pass and fold of ONE
+// BatchNorm stop at this rank's fp64 moments (count, sum, M2 about its own mean | count, sum dy, sum dy xhat), the caller gathers every
+// rank's, and pmt_hapbn_merge_kernel finishes them in rank order -- 3 K + 1 launches each way; one rank gives the bits of the one call.
 #define PMT_OWN_WAVE_SHAPE
 #define PMT_WAVES 4
 #define PMT_RT 2
@@ -124,9 +130,12 @@ DEV double fold_sum(double v, double* sh) {  // a fixed tree over the workgroup;
 // backward == 0: (mean_i, M2_i) -> st[c] = mean, st[C + c] = rstd, st[2 C + c] = unbiased variance
 // backward == 1: (sum dy, sum dy xhat) -> st[3 C + c] = c1, st[4 C + c] = c2;  gtheta[b_src + c] += sum dy, gtheta[w_src + c] += sum dy xhat
 // (this launch is alone on its stream position and owns channel c: plain adds)
+// mom != nullptr (the stepped form): nothing is finished -- the fold's three fp64 numbers of this channel go to mom[k * C + c], k = 0 the
+// count N, 1 the sum (forward sum n_i m_i, backward sum dy), 2 forward the M2 about sum / N, backward sum dy xhat: what
+// pmt_hapbn_merge_kernel takes from every rank.  st and gtheta are not touched then.
 extern "C" __global__ __launch_bounds__(BN_FOLD_THREADS) void pmt_hapbn_fold_kernel(
     const float* __restrict__ part, int nblocks, int vpb, int n, int len, int C, float* __restrict__ st, int backward,
-    float* __restrict__ gtheta, int w_src, int b_src) {
+    float* __restrict__ gtheta, int w_src, int b_src, double* __restrict__ mom) {
     __shared__ double sh[BN_FOLD_THREADS];
     const int c = blockIdx.x;
     const float* p = part + (size_t)c * nblocks * 2;
@@ -135,14 +144,21 @@ extern "C" __global__ __launch_bounds__(BN_FOLD_THREADS) void pmt_hapbn_fold_ker
         double acc = 0.0;
         for (int i = threadIdx.x; i < nblocks; i += BN_FOLD_THREADS)
             acc += (double)(min(vpb, n - i * vpb) * len) * (double)p[2 * i];
-        const double mean = fold_sum(acc, sh) / N;
+        const double sum = fold_sum(acc, sh);
+        const double mean = sum / N;
         acc = 0.0;
         for (int i = threadIdx.x; i < nblocks; i += BN_FOLD_THREADS) {
             const double d = (double)p[2 * i] - mean;
             acc += (double)p[2 * i + 1] + (double)(min(vpb, n - i * vpb) * len) * d * d;
         }
         const double m2 = fold_sum(acc, sh);
-        if (threadIdx.x == 0) {
+        if (mom) {
+            if (threadIdx.x == 0) {
+                mom[c] = N;
+                mom[C + c] = sum;
+                mom[2 * C + c] = m2;
+            }
+        } else if (threadIdx.x == 0) {
             st[c] = (float)mean;
             st[C + c] = (float)(1.0 / sqrt(m2 / N + (double)PMT_CNN_BN_EPS));
             st[2 * C + c] = (float)(m2 / (N - 1.0));
@@ -155,13 +171,78 @@ extern "C" __global__ __launch_bounds__(BN_FOLD_THREADS) void pmt_hapbn_fold_ker
         }
         a1 = fold_sum(a1, sh);
         a2 = fold_sum(a2, sh);
-        if (threadIdx.x == 0) {
+        if (mom) {
+            if (threadIdx.x == 0) {
+                mom[c] = N;
+                mom[C + c] = a1;
+                mom[2 * C + c] = a2;
+            }
+        } else if (threadIdx.x == 0) {
             st[3 * C + c] = (float)(a1 / N);
             st[4 * C + c] = (float)(a2 / N);
             gtheta[b_src + c] += (float)a1;
             gtheta[w_src + c] += (float)a2;
         }
     }
+}
+
+// The moments of `ranks` ranks (mom[(r * 3 + k) * C + c], written by pmt_hapbn_fold_kernel on each and gathered by the caller) -> the
+// statistics of their union.  A thread per channel walks the ranks in order: fp64, no atomics, the same bits wherever it runs.  The sums
+// start from rank 0's numbers, not from 0.0, so that one rank gives exactly the one-call fold: mean = sum / N is its expression, and
+// sum_0 / cnt_0 - mean is exactly 0.  A rank without values (cnt = 0) has no mean and contributes nothing.
+// backward == 1: only rank `self`'s own sums go into gtheta (the gradient all-reduce adds the other ranks' later).
+extern "C" __global__ __launch_bounds__(BN_FOLD_THREADS) void pmt_hapbn_merge_kernel(
+    const double* __restrict__ mom, int ranks, int self, int C, float* __restrict__ st, int backward, float* __restrict__ gtheta,
+    int w_src, int b_src) {
+    const int c = blockIdx.x * BN_FOLD_THREADS + threadIdx.x;
+    if (c >= C) return;
+    double N = mom[c], s1 = mom[C + c], s2 = mom[2 * C + c];
+    for (int r = 1; r < ranks; ++r) {
+        const double* m = mom + (size_t)r * 3 * C;
+        N += m[c];
+        s1 += m[C + c];
+        if (backward) s2 += m[2 * C + c];
+    }
+    if (!backward) {
+        const double mean = s1 / N;
+        double m2 = 0.0;
+        bool first = true;
+        for (int r = 0; r < ranks; ++r) {
+            const double* m = mom + (size_t)r * 3 * C;
+            const double cnt = m[c];
+            if (cnt > 0.0) {
+                const double d = m[C + c] / cnt - mean;
+                const double term = m[2 * C + c] + cnt * d * d;
+                m2 = first ? term : m2 + term;
+                first = false;
+            }
+        }
+        st[c] = (float)mean;
+        st[C + c] = (float)(1.0 / sqrt(m2 / N + (double)PMT_CNN_BN_EPS));
+        st[2 * C + c] = (float)(m2 / (N - 1.0));
+    } else {
+        const double* own = mom + (size_t)self * 3 * C;
+        st[3 * C + c] = (float)(s1 / N);
+        st[4 * C + c] = (float)(s2 / N);
+        gtheta[b_src + c] += (float)own[C + c];
+        gtheta[w_src + c] += (float)own[2 * C + c];
+    }
+}
+
+// The private rows of the backward's full pass -> gtheta[lo + i] += their sum, a thread per parameter, in an order that depends on the
+// number of rows alone: two launches of this kernel.  First every chunk of BN_WGRAD_CHUNK consecutive rows (blockIdx.y) is summed in row
+// order into its first row (dst == nullptr; at vpb = 2 a batch of 65 536 variants has 32 768 rows: one thread walking them all takes
+// 10 ms), then the chunks' first rows (row_step = the chunk) are summed in order and added to the gradient.
+#define BN_WGRAD_CHUNK 64
+extern "C" __global__ __launch_bounds__(BN_FOLD_THREADS) void pmt_hapbn_wgrad_fold_kernel(
+    float* __restrict__ priv, int nrows, int row_step, int span, float* __restrict__ dst) {
+    const int i = blockIdx.x * BN_FOLD_THREADS + threadIdx.x;
+    if (i >= span) return;
+    const int r0 = dst ? 0 : blockIdx.y * BN_WGRAD_CHUNK, r1 = dst ? nrows : min(r0 + BN_WGRAD_CHUNK, nrows);
+    float acc = 0.f;
+    for (int r = r0; r < r1; r += row_step) acc += priv[(size_t)r * span + i];
+    if (dst) dst[i] += acc;
+    else priv[(size_t)r0 * span + i] = acc;  // (this thread alone reads and writes column i of its chunk)
 }
 
 struct BnFwdShared {
@@ -226,14 +307,19 @@ struct BnBwdShared {
 };
 
 // Backward over the training descriptor; LDS as pmt_cnn_backward_kernel (every layer output, stride sum_act, plus two gradient buffers).
-// stop < 0: the full pass -- every layer, weight gradients emitted, a BatchNorm propagates with its c1 / c2.
+// stop < 0: the full pass -- every layer, weight gradients emitted (into `priv`, below), a BatchNorm propagates with its c1 / c2.
 // stop >= 0: layer `stop` is a BatchNorm whose sums are wanted: walks back to it without emitting anything and writes the partials.
 extern "C" __global__ __launch_bounds__(PMT_THREADS, 2) void pmt_hapbn_backward_kernel(
     const PmtModel* __restrict__ M, const PmtCnn* __restrict__ Cp, const float* __restrict__ theta, const float* __restrict__ packed,
     const long long* __restrict__ hap, long long hap_stride, int n, int vpb, int stop, const float* __restrict__ stats,
-    float* __restrict__ part, const float* __restrict__ d_out, long long d_out_stride, float* __restrict__ gtheta) {
+    float* __restrict__ part, const float* __restrict__ d_out, long long d_out_stride, float* gtheta, float* __restrict__ priv, int priv_lo,
+    int priv_span) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ __attribute__((aligned(16))) BnBwdShared sh;
+    // the full pass: this workgroup's weight / bias gradients go to a zeroed row of its own, [priv_lo, priv_lo + priv_span) of the flat
+    // buffer, where every address has ONE writer (a wave owns its blocks of a weight gradient, a thread its elements of the linear's) adding
+    // in program order; pmt_hapbn_wgrad_fold_kernel sums the rows in workgroup order.  No float atomic meets another: the same bits on every call.
+    if (priv) gtheta = priv + (size_t)blockIdx.x * priv_span - priv_lo;
     const PmtCnn& C = *Cp;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, wave = uniform((int)(tid >> 6));
     const int v0 = blockIdx.x * vpb;
@@ -440,6 +526,9 @@ static int bn_check(const PmtModel* m, const PmtCnn* c) {
             const PmtLinear* w = &m->lin[L->lin];
             if (w->in_dim != L->in_ch * L->kernel || w->out_dim != L->out_ch || w->b_pvec < 0) return PMT_E_INVALID;
             if (L->b_src < 0 || L->b_src + L->out_ch > m->theta_size) return PMT_E_INVALID;  // (the forward adds the bias from theta, last)
+            // (the backward's private gradient rows span the LAYER's offsets: they must be where the PmtLinear's gradients go)
+            if (L->w_src < 0 || L->w_src != w->w_src || L->b_src != w->b_src || (long long)L->w_src + (long long)w->in_dim * w->out_dim > m->theta_size)
+                return PMT_E_INVALID;
             if (w->in_dim > PMT_MAX_CNN_TAPS || w->out_dim > PMT_MAX_WIDTH) return PMT_E_UNSUPPORTED;
             if (L->in_ch * L->in_len >= 65536 || L->kernel * L->dilation >= 64 || L->padding >= 64 || L->stride < 1) return PMT_E_UNSUPPORTED;
         }
@@ -458,12 +547,35 @@ static size_t bn_part_floats(const PmtCnn* c, int n, int vpb) {  // the widest B
     return 2 * (size_t)maxc * (size_t)((n + vpb - 1) / vpb);
 }
 
+// [lo, hi) of the flat buffer: the weights and biases of the convolutions and the linear, what the backward's full pass adds gradients to
+static void bn_wgrad_span(const PmtCnn* c, int* lo, int* hi) {
+    *lo = INT32_MAX;
+    *hi = 0;
+    for (int l = 0; l < c->n_layers; ++l) {
+        const PmtCnnLayer* L = &c->layers[l];
+        if (L->kind != PMT_CNN_CONV && L->kind != PMT_CNN_LINEAR) continue;
+        const int nw = L->kind == PMT_CNN_CONV ? L->in_ch * L->kernel * L->out_ch : L->in_ch * L->in_len * L->out_ch * L->out_len;
+        const int nb = L->kind == PMT_CNN_CONV ? L->out_ch : L->out_ch * L->out_len;
+        if (L->w_src < *lo) *lo = L->w_src;
+        if (L->b_src < *lo) *lo = L->b_src;
+        if (L->w_src + nw > *hi) *hi = L->w_src + nw;
+        if (L->b_src + nb > *hi) *hi = L->b_src + nb;
+    }
+    if (*hi <= *lo) *lo = *hi = 0;
+}
+
+static size_t bn_priv_floats(const PmtCnn* c, int n, int vpb) {  // a row of the span per workgroup of the backward's full pass
+    int lo, hi;
+    bn_wgrad_span(c, &lo, &hi);
+    return (size_t)(hi - lo) * (size_t)((n + vpb - 1) / vpb);
+}
+
 extern "C" size_t pmt_cnn_bn_workspace_floats(const PmtCnn* c, int32_t n) {
     if (!c || n < 1) return 0;
     const int vf = bn_fwd_vpb(c), vb = bn_bwd_vpb(c);
     if (vf < 1 || vb < 1) return 0;
-    const size_t a = bn_part_floats(c, n, vf), b = bn_part_floats(c, n, vb);
-    return a > b ? a : b;
+    const size_t a = bn_part_floats(c, n, vf), b = bn_part_floats(c, n, vb), p = bn_priv_floats(c, n, vb);
+    return a > b ? (a > p ? a : p) : (b > p ? b : p);
 }
 
 static int bn_common_check(const PmtModel* mh, const PmtCnn* c, int32_t n) {
@@ -476,36 +588,90 @@ static int bn_common_check(const PmtModel* mh, const PmtCnn* c, int32_t n) {
 }
 
 static int bn_fold(const PmtCnnLayer* L, const float* part, int nblocks, int vpb, int n, float* stats, int backward, float* gtheta,
-                   hipStream_t s) {
+                   double* moments, hipStream_t s) {
     hipLaunchKernelGGL(pmt_hapbn_fold_kernel, dim3(L->in_ch), dim3(BN_FOLD_THREADS), 0, s, part, nblocks, vpb, (int)n, (int)L->in_len,
-                       (int)L->in_ch, stats + L->reserved[0], backward, gtheta, (int)L->w_src, (int)L->b_src);
+                       (int)L->in_ch, stats ? stats + L->reserved[0] : nullptr, backward, gtheta, (int)L->w_src, (int)L->b_src, moments);
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
+}
+
+// One launch of pmt_hapbn_forward_kernel / pmt_hapbn_backward_kernel: up to layer `stop` (a BatchNorm: partials into `part`) or the full pass
+struct BnPass {
+    const PmtModel* model_dev;
+    const PmtCnn *cnn_host, *cnn_dev;
+    const float *theta, *packed;
+    const int64_t* hap;
+    int64_t hap_stride;
+    int n, vpb;
+    hipStream_t s;
+    int nblocks() const { return (n + vpb - 1) / vpb; }
+};
+
+static int bn_forward_pass(const BnPass& p, int stop, const float* stats, float* part, float* out, int64_t out_stride) {
+    const size_t lds = (size_t)p.vpb * 2 * p.cnn_host->max_act * sizeof(float);
+    hipLaunchKernelGGL(pmt_hapbn_forward_kernel, dim3(p.nblocks()), dim3(PMT_THREADS), lds, p.s, p.model_dev, p.cnn_dev, p.theta, p.packed,
+                       (const long long*)p.hap, (long long)p.hap_stride, p.n, p.vpb, stop, stats, part, out, (long long)out_stride);
+    return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
+}
+
+static int bn_backward_pass(const BnPass& p, int stop, const float* stats, float* part, const float* d_out, int64_t d_out_stride,
+                            float* gtheta, float* priv = nullptr, int priv_lo = 0, int priv_span = 0) {
+    const size_t lds = (size_t)p.vpb * ((size_t)p.cnn_host->sum_act + 2 * (size_t)p.cnn_host->max_act) * sizeof(float);
+    hipLaunchKernelGGL(pmt_hapbn_backward_kernel, dim3(p.nblocks()), dim3(PMT_THREADS), lds, p.s, p.model_dev, p.cnn_dev, p.theta, p.packed,
+                       (const long long*)p.hap, (long long)p.hap_stride, p.n, p.vpb, stop, stats, part, d_out, (long long)d_out_stride, gtheta,
+                       priv, priv_lo, priv_span);
+    return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
+}
+
+// The backward's full pass: the workspace (the partials in it are spent by now) becomes a zeroed private gradient row per workgroup,
+// folded into grad_theta in workgroup order.  A fill, the pass, the fold's two launches.
+static int bn_backward_full_pass(const BnPass& p, const float* stats, const float* d_out, int64_t d_out_stride, float* gtheta, float* workspace,
+                                 size_t workspace_floats) {
+    int lo, hi;
+    bn_wgrad_span(p.cnn_host, &lo, &hi);
+    const int span = hi - lo;
+    if (span <= 0) return bn_backward_pass(p, -1, stats, nullptr, d_out, d_out_stride, gtheta);  // (no layer with weights: nothing is emitted)
+    const size_t need = (size_t)span * (size_t)p.nblocks();
+    if (!workspace || workspace_floats < need) return PMT_E_WORKSPACE;
+    if (hipMemsetAsync(workspace, 0, need * sizeof(float), p.s) != hipSuccess) return PMT_E_LAUNCH;
+    const int rc = bn_backward_pass(p, -1, stats, nullptr, d_out, d_out_stride, gtheta, workspace, lo, span);
+    if (rc) return rc;
+    const int cols = (span + BN_FOLD_THREADS - 1) / BN_FOLD_THREADS, chunks = (p.nblocks() + BN_WGRAD_CHUNK - 1) / BN_WGRAD_CHUNK;
+    hipLaunchKernelGGL(pmt_hapbn_wgrad_fold_kernel, dim3(cols, chunks), dim3(BN_FOLD_THREADS), 0, p.s, workspace, p.nblocks(), 1, span,
+                       (float*)nullptr);
+    if (hipGetLastError() != hipSuccess) return PMT_E_LAUNCH;
+    hipLaunchKernelGGL(pmt_hapbn_wgrad_fold_kernel, dim3(cols), dim3(BN_FOLD_THREADS), 0, p.s, workspace, p.nblocks(), BN_WGRAD_CHUNK, span,
+                       gtheta + lo);
+    return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
+}
+
+// the arguments every entry point shares; `backward` picks the chunk size; with `need_ws` the partials of the widest BatchNorm must fit
+static int bn_pass_init(BnPass* p, int backward, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev, const float* theta,
+                        const float* packed, const int64_t* hap, int64_t hap_stride, int32_t n, bool need_ws, const float* workspace,
+                        size_t workspace_floats, void* stream) {
+    if (!model_dev || !cnn_dev || !theta || !packed || !hap) return PMT_E_INVALID;
+    const int vpb = backward ? bn_bwd_vpb(cnn_host) : bn_fwd_vpb(cnn_host);
+    if (vpb < 1) return PMT_E_UNSUPPORTED;
+    const size_t need = need_ws ? bn_part_floats(cnn_host, n, vpb) : 0;
+    if (need > 0 && (!workspace || workspace_floats < need)) return PMT_E_WORKSPACE;
+    *p = BnPass{model_dev, cnn_host, cnn_dev, theta, packed, hap, hap_stride, (int)n, vpb, reinterpret_cast<hipStream_t>(stream)};
+    return PMT_OK;
 }
 
 extern "C" int pmt_cnn_bn_forward(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
                                   const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
                                   float* out, int64_t out_stride, float* stats, float* workspace, size_t workspace_floats, void* stream) {
-    const int rc = bn_common_check(model_host, cnn_host, n);
+    int rc = bn_common_check(model_host, cnn_host, n);
     if (rc) return rc;
     if (n == 0) return PMT_OK;
-    if (!model_dev || !cnn_dev || !theta || !packed || !haplotypes || !out || !stats) return PMT_E_INVALID;
-    const int vpb = bn_fwd_vpb(cnn_host);
-    if (vpb < 1) return PMT_E_UNSUPPORTED;
-    const size_t need = bn_part_floats(cnn_host, n, vpb);
-    if (need > 0 && (!workspace || workspace_floats < need)) return PMT_E_WORKSPACE;
-    const int nblocks = (n + vpb - 1) / vpb;
-    const size_t lds = (size_t)vpb * 2 * cnn_host->max_act * sizeof(float);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!out || !stats) return PMT_E_INVALID;
+    BnPass p;
+    if ((rc = bn_pass_init(&p, 0, model_dev, cnn_host, cnn_dev, theta, packed, haplotypes, hap_stride, n, true, workspace, workspace_floats, stream)))
+        return rc;
     for (int l = 0; l <= cnn_host->n_layers; ++l) {
         if (l < cnn_host->n_layers && cnn_host->layers[l].kind != PMT_CNN_BATCHNORM) continue;
-        hipLaunchKernelGGL(pmt_hapbn_forward_kernel, dim3(nblocks), dim3(PMT_THREADS), lds, s, model_dev, cnn_dev, theta, packed,
-                           (const long long*)haplotypes, (long long)hap_stride, (int)n, vpb, l, (const float*)stats, workspace, out,
-                           (long long)out_stride);
-        if (hipGetLastError() != hipSuccess) return PMT_E_LAUNCH;
-        if (l < cnn_host->n_layers) {
-            const int rf = bn_fold(&cnn_host->layers[l], workspace, nblocks, vpb, n, stats, 0, nullptr, s);
-            if (rf) return rf;
-        }
+        if ((rc = bn_forward_pass(p, l, stats, workspace, out, out_stride))) return rc;
+        if (l < cnn_host->n_layers && (rc = bn_fold(&cnn_host->layers[l], workspace, p.nblocks(), p.vpb, n, stats, 0, nullptr, nullptr, p.s)))
+            return rc;
     }
     return PMT_OK;
 }
@@ -514,27 +680,91 @@ extern "C" int pmt_cnn_bn_backward(const PmtModel* model_host, const PmtModel* m
                                    const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
                                    const float* d_out, int64_t d_out_stride, float* stats, float* grad_theta, float* workspace,
                                    size_t workspace_floats, void* stream) {
-    const int rc = bn_common_check(model_host, cnn_host, n);
+    int rc = bn_common_check(model_host, cnn_host, n);
     if (rc) return rc;
     if (n == 0) return PMT_OK;
-    if (!model_dev || !cnn_dev || !theta || !packed || !haplotypes || !d_out || !stats || !grad_theta) return PMT_E_INVALID;
-    const int vpb = bn_bwd_vpb(cnn_host);
-    if (vpb < 1) return PMT_E_UNSUPPORTED;
-    const size_t need = bn_part_floats(cnn_host, n, vpb);
-    if (need > 0 && (!workspace || workspace_floats < need)) return PMT_E_WORKSPACE;
-    const int nblocks = (n + vpb - 1) / vpb;
-    const size_t lds = (size_t)vpb * ((size_t)cnn_host->sum_act + 2 * (size_t)cnn_host->max_act) * sizeof(float);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    for (int l = cnn_host->n_layers - 1; l >= -1; --l) {
-        if (l >= 0 && cnn_host->layers[l].kind != PMT_CNN_BATCHNORM) continue;
-        hipLaunchKernelGGL(pmt_hapbn_backward_kernel, dim3(nblocks), dim3(PMT_THREADS), lds, s, model_dev, cnn_dev, theta, packed,
-                           (const long long*)haplotypes, (long long)hap_stride, (int)n, vpb, l, (const float*)stats, workspace, d_out,
-                           (long long)d_out_stride, grad_theta);
-        if (hipGetLastError() != hipSuccess) return PMT_E_LAUNCH;
-        if (l >= 0) {
-            const int rf = bn_fold(&cnn_host->layers[l], workspace, nblocks, vpb, n, stats, 1, grad_theta, s);
-            if (rf) return rf;
-        }
+    if (!d_out || !stats || !grad_theta) return PMT_E_INVALID;
+    BnPass p;
+    if ((rc = bn_pass_init(&p, 1, model_dev, cnn_host, cnn_dev, theta, packed, haplotypes, hap_stride, n, true, workspace, workspace_floats, stream)))
+        return rc;
+    if (workspace_floats < bn_priv_floats(cnn_host, n, p.vpb)) return PMT_E_WORKSPACE;
+    for (int l = cnn_host->n_layers - 1; l >= 0; --l) {
+        if (cnn_host->layers[l].kind != PMT_CNN_BATCHNORM) continue;
+        if ((rc = bn_backward_pass(p, l, stats, workspace, d_out, d_out_stride, grad_theta))) return rc;
+        if ((rc = bn_fold(&cnn_host->layers[l], workspace, p.nblocks(), p.vpb, n, stats, 1, grad_theta, nullptr, p.s))) return rc;
     }
+    return bn_backward_full_pass(p, stats, d_out, d_out_stride, grad_theta, workspace, workspace_floats);
+}
+
+// ---- the stepped form: the caller's exchange of moments goes between these calls (include/permutect_amd.h) -------------------------------
+static int bn_step_check(const PmtModel* mh, const PmtCnn* c, int32_t n, int32_t layer) {  // layer < 0: a full pass, no layer to name
+    const int rc = bn_check(mh, c);
+    if (rc) return rc;
+    if (n < 1) return PMT_E_INVALID;
+    if (layer >= 0 && (layer >= c->n_layers || c->layers[layer].kind != PMT_CNN_BATCHNORM)) return PMT_E_INVALID;
     return PMT_OK;
+}
+
+extern "C" int pmt_cnn_bn_forward_moments(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                                          const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                                          int32_t layer, const float* stats, double* moments, float* workspace, size_t workspace_floats,
+                                          void* stream) {
+    int rc = layer < 0 ? PMT_E_INVALID : bn_step_check(model_host, cnn_host, n, layer);
+    if (rc) return rc;
+    if (!stats || !moments) return PMT_E_INVALID;
+    BnPass p;
+    if ((rc = bn_pass_init(&p, 0, model_dev, cnn_host, cnn_dev, theta, packed, haplotypes, hap_stride, n, true, workspace, workspace_floats, stream)))
+        return rc;
+    if ((rc = bn_forward_pass(p, layer, stats, workspace, nullptr, 0))) return rc;
+    return bn_fold(&cnn_host->layers[layer], workspace, p.nblocks(), p.vpb, n, nullptr, 0, nullptr, moments, p.s);
+}
+
+extern "C" int pmt_cnn_bn_backward_moments(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                                           const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                                           int32_t layer, const float* d_out, int64_t d_out_stride, const float* stats, double* moments,
+                                           float* workspace, size_t workspace_floats, void* stream) {
+    int rc = layer < 0 ? PMT_E_INVALID : bn_step_check(model_host, cnn_host, n, layer);
+    if (rc) return rc;
+    if (!d_out || !stats || !moments) return PMT_E_INVALID;
+    BnPass p;
+    if ((rc = bn_pass_init(&p, 1, model_dev, cnn_host, cnn_dev, theta, packed, haplotypes, hap_stride, n, true, workspace, workspace_floats, stream)))
+        return rc;
+    if ((rc = bn_backward_pass(p, layer, stats, workspace, d_out, d_out_stride, nullptr))) return rc;  // (a sums pass emits no gradient)
+    return bn_fold(&cnn_host->layers[layer], workspace, p.nblocks(), p.vpb, n, nullptr, 1, nullptr, moments, p.s);
+}
+
+extern "C" int pmt_cnn_bn_merge(const PmtModel* model_host, const PmtCnn* cnn_host, int32_t layer, int32_t n, const double* moments,
+                                int32_t ranks, int32_t rank, int32_t backward, float* stats, float* grad_theta, void* stream) {
+    const int rc = layer < 0 ? PMT_E_INVALID : bn_step_check(model_host, cnn_host, n, layer);
+    if (rc) return rc;
+    const PmtCnnLayer* L = &cnn_host->layers[layer];
+    if (ranks < 1 || rank < 0 || rank >= ranks || !moments || !stats || (backward && !grad_theta)) return PMT_E_INVALID;
+    if (ranks == 1 && (long long)n * L->in_len < 2) return PMT_E_INVALID;  // a single value per channel has no variance (torch: ValueError)
+    hipLaunchKernelGGL(pmt_hapbn_merge_kernel, dim3((L->in_ch + BN_FOLD_THREADS - 1) / BN_FOLD_THREADS), dim3(BN_FOLD_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), moments, (int)ranks, (int)rank, (int)L->in_ch, stats + L->reserved[0],
+                       backward ? 1 : 0, grad_theta, (int)L->w_src, (int)L->b_src);
+    return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
+}
+
+extern "C" int pmt_cnn_bn_forward_full(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                                       const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                                       float* out, int64_t out_stride, const float* stats, void* stream) {
+    int rc = bn_step_check(model_host, cnn_host, n, -1);
+    if (rc) return rc;
+    if (!out || !stats) return PMT_E_INVALID;
+    BnPass p;
+    if ((rc = bn_pass_init(&p, 0, model_dev, cnn_host, cnn_dev, theta, packed, haplotypes, hap_stride, n, false, nullptr, 0, stream))) return rc;
+    return bn_forward_pass(p, cnn_host->n_layers, stats, nullptr, out, out_stride);
+}
+
+extern "C" int pmt_cnn_bn_backward_full(const PmtModel* model_host, const PmtModel* model_dev, const PmtCnn* cnn_host, const PmtCnn* cnn_dev,
+                                        const float* theta, const float* packed, const int64_t* haplotypes, int64_t hap_stride, int32_t n,
+                                        const float* d_out, int64_t d_out_stride, const float* stats, float* grad_theta, float* workspace,
+                                        size_t workspace_floats, void* stream) {
+    int rc = bn_step_check(model_host, cnn_host, n, -1);
+    if (rc) return rc;
+    if (!d_out || !stats || !grad_theta) return PMT_E_INVALID;
+    BnPass p;
+    if ((rc = bn_pass_init(&p, 1, model_dev, cnn_host, cnn_dev, theta, packed, haplotypes, hap_stride, n, false, nullptr, 0, stream))) return rc;
+    return bn_backward_full_pass(p, stats, d_out, d_out_stride, grad_theta, workspace, workspace_floats);
 }

@@ -207,6 +207,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_scan_counts", "pmt_forward", "pmt_backward", "pmt_clip_adamw",
            "pmt_dropout_mask", "pmt_rows_stash_bytes", "pmt_rows_forward", "pmt_rows_backward", "pmt_rows_workspace_floats", "pmt_cnn_forward", "pmt_cnn_backward", "pmt_cnn_stash_floats", "pmt_cnn_workspace_floats",
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
+           "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
            "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_update", "pmt_record_losses", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
@@ -260,6 +261,12 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_cnn_bn_forward.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, C.c_size_t, vp]
     lib.pmt_cnn_bn_backward.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, C.c_size_t, vp]
     lib.pmt_cnn_bn_workspace_floats.argtypes = [P(PmtCnn), i32]
+    # the stepped form (statistics over several ranks' batches): ..., n, layer, [d_out, stride,] stats, moments, workspace, floats, stream
+    lib.pmt_cnn_bn_forward_moments.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, C.c_size_t, vp]
+    lib.pmt_cnn_bn_backward_moments.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, C.c_size_t, vp]
+    lib.pmt_cnn_bn_merge.argtypes = [P(PmtModel), P(PmtCnn), i32, i32, vp, i32, i32, i32, vp, vp, vp]
+    lib.pmt_cnn_bn_forward_full.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, vp, i64, vp, vp]
+    lib.pmt_cnn_bn_backward_full.argtypes = [P(PmtModel), vp, P(PmtCnn), vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, C.c_size_t, vp]
     lib.pmt_cnn_bn_workspace_floats.restype = C.c_size_t
     lib.pmt_cnn_stash_floats.restype = C.c_size_t
     lib.pmt_rows_stash_bytes.argtypes = [P(PmtModel), i32, i32]

@@ -58,6 +58,9 @@ class ReadSetEngine:
         # this call runs the haplotype CNN's BatchNorms on BATCH statistics (set by ArtifactModel._encode on every forward: train mode of a
         # model that opted in, ArtifactModel.train_cnn_batch_norm; plan.cnn_train_desc has been lowered by then)
         self.cnn_batch_stats = False
+        # ... and on the statistics of EVERY rank's batch (ArtifactModel.train_cnn_batch_norm(sync=True); set with cnn_batch_stats), over
+        # `cnn_bn_group` (None: the default process group)
+        self.cnn_bn_sync, self.cnn_bn_group = False, None
         # ONE persistent fault word for every joined launch of this engine (PmtBatch.join_fault): a launch whose bounded wait for
         # another workgroup gave up stores 1 there and its numbers are wrong.  Read by check_join_fault() wherever the callers
         # synchronise anyway: end of a training / evaluation epoch, end of a filtering pass, bench.py, the tests.
@@ -139,22 +142,64 @@ class ReadSetEngine:
             self._cnn_fold, self._cnn_fold_key = (theta_f, packed_f), key
         return self._cnn_fold
 
+    def _cnn_bn_common(self, c, hap: Tensor):
+        """the leading arguments of every pmt_cnn_bn_* pass over `hap`"""
+        plan = self.plan
+        return (C.byref(plan.desc), plan.desc_dev.data_ptr(), C.byref(c), plan.cnn_train_dev.data_ptr(), self.space.theta.data_ptr(),
+                plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), hap.shape[0])
+
+    def _cnn_bn_ranks(self):
+        """(world size, this rank) of the group the BatchNorms' statistics are synchronised over"""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise L.PmtError("synchronised BatchNorm statistics need an initialised torch.distributed process group")
+        return dist.get_world_size(self.cnn_bn_group), dist.get_rank(self.cnn_bn_group)
+
+    def _cnn_bn_exchange(self, c, bn_layers, ranks: int):
+        """One zeroed float64 buffer for the moments of every BatchNorm of a pass: per BatchNorm a [ranks, 3, C] block (one fill launch)."""
+        sizes = [ranks * 3 * c.layers[i].in_ch for i in bn_layers]
+        return torch.zeros(sum(sizes), dtype=torch.float64, device=self.device).split(sizes)
+
     def cnn_bn_forward(self, hap: Tensor, out_ptr: int, out_stride: int) -> Tensor:
         """The haplotype CNN on batch statistics (pmt_cnn_bn_forward: 2 K + 1 launches for K BatchNorms) into the rows at `out_ptr`, then the
         running statistics of every BatchNorm as torch updates them in train mode (running <- (1 - momentum) running + momentum batch, the
         UNBIASED batch variance; num_batches_tracked += 1): two more launches, no host synchronisation.  Returns the statistics buffer,
-        which the backward of the same call reads and completes."""
+        which the backward of the same call reads and completes.
+
+        With `cnn_bn_sync` the statistics are those of the union of every rank's batch (the stepped entry points): per BatchNorm, in stack
+        order, this rank's moments go into its slot of a zeroed [ranks, 3, C] float64 buffer, a SUM all-reduce on the current stream
+        gathers the slots (x + 0 is exact: the result does not depend on the reduction order), and a merge in rank order gives every rank
+        the same bits; then the full pass.  3 K + 1 launches and K collectives; the running statistics move to the merged values, so they
+        stay identical on every rank.  Every rank must make this call, with a batch of at least one variant."""
         plan, n = self.plan, hap.shape[0]
         c = plan.cnn_train_desc(None)
-        for layer, (bn, _) in zip([c.layers[i] for i in range(c.n_layers) if c.layers[i].kind == L.CNN_BATCHNORM], plan.cnn_train_bns):
-            if n * layer.in_len < 2:  # torch.nn.functional.batch_norm in train mode
+        bn_layers = [i for i in range(c.n_layers) if c.layers[i].kind == L.CNN_BATCHNORM]
+        ranks, rank = self._cnn_bn_ranks() if self.cnn_bn_sync else (1, 0)
+        if self.cnn_bn_sync and n < 1:
+            # (its autograd graph would hold no backward for the haplotype CNN: the other ranks would wait in the backward's collectives)
+            raise L.PmtError("synchronised BatchNorm statistics: this rank's batch is empty; every rank takes part in every train-mode "
+                             "forward and backward with at least one variant")
+        for i in bn_layers:
+            layer = c.layers[i]
+            if ranks == 1 and n * layer.in_len < 2:  # torch.nn.functional.batch_norm in train mode (more ranks: every rank holds a value)
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size [{n}, {layer.in_ch}"
                                  + (f", {layer.in_len}]" if layer.in_len > 1 else "]"))
         stats = torch.empty(max(c.reserved[0], 4), dtype=torch.float32, device=self.device)
         ws = torch.empty(max(self.lib.pmt_cnn_bn_workspace_floats(C.byref(c), n), 4), dtype=torch.float32, device=self.device)
-        L.check(self.lib.pmt_cnn_bn_forward(C.byref(plan.desc), plan.desc_dev.data_ptr(), C.byref(c), plan.cnn_train_dev.data_ptr(),
-                                            self.space.theta.data_ptr(), plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, out_ptr,
-                                            out_stride, stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "pmt_cnn_bn_forward")
+        if not self.cnn_bn_sync:
+            L.check(self.lib.pmt_cnn_bn_forward(*self._cnn_bn_common(c, hap), out_ptr, out_stride, stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _stream()), "pmt_cnn_bn_forward")
+        else:
+            import torch.distributed as dist
+            for i, mom in zip(bn_layers, self._cnn_bn_exchange(c, bn_layers, ranks)):
+                own = mom.data_ptr() + rank * 3 * c.layers[i].in_ch * 8
+                L.check(self.lib.pmt_cnn_bn_forward_moments(*self._cnn_bn_common(c, hap), i, stats.data_ptr(), own, ws.data_ptr(), ws.numel(),
+                                                            _stream()), "pmt_cnn_bn_forward_moments")
+                dist.all_reduce(mom, op=dist.ReduceOp.SUM, group=self.cnn_bn_group)
+                L.check(self.lib.pmt_cnn_bn_merge(C.byref(plan.desc), C.byref(c), i, n, mom.data_ptr(), ranks, rank, 0, stats.data_ptr(), None,
+                                                  _stream()), "pmt_cnn_bn_merge")
+            L.check(self.lib.pmt_cnn_bn_forward_full(*self._cnn_bn_common(c, hap), out_ptr, out_stride, stats.data_ptr(), _stream()),
+                    "pmt_cnn_bn_forward_full")
         with torch.no_grad():
             running, batch = [], []
             for bn, off in plan.cnn_train_bns:
@@ -173,16 +218,32 @@ class ReadSetEngine:
         self._cnn_fold_key = None
         return stats
 
-    def cnn_bn_backward(self, hap: Tensor, d_out_ptr: int, d_out_stride: int, stats: Tensor):
+    def cnn_bn_backward(self, hap: Tensor, d_out_ptr: int, d_out_stride: int, stats: Tensor, sync: bool = False):
         """pmt_cnn_bn_backward: recomputes the forward from `stats` (the running statistics are not touched again) and adds every gradient
-        of the haplotype CNN, its BatchNorms' weight / bias included, to the flat gradient buffer"""
+        of the haplotype CNN, its BatchNorms' weight / bias included, to the flat gradient buffer.  `sync`: the forward of this call ran
+        on synchronised statistics, so the sums of every BatchNorm are those of every rank's batch too -- K more collectives, last
+        BatchNorm first; the BatchNorms' own weight / bias gradients stay this rank's (the gradient all-reduce sums them)."""
         plan, n = self.plan, hap.shape[0]
         c = plan.cnn_train_desc(None)
         ws = torch.empty(max(self.lib.pmt_cnn_bn_workspace_floats(C.byref(c), n), 4), dtype=torch.float32, device=self.device)
-        L.check(self.lib.pmt_cnn_bn_backward(C.byref(plan.desc), plan.desc_dev.data_ptr(), C.byref(c), plan.cnn_train_dev.data_ptr(),
-                                             self.space.theta.data_ptr(), plan.packed.data_ptr(), hap.data_ptr(), hap.stride(0), n, d_out_ptr,
-                                             d_out_stride, stats.data_ptr(), self.space.gtheta.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             _stream()), "pmt_cnn_bn_backward")
+        gtheta = self.space.gtheta.data_ptr()
+        if not sync:
+            L.check(self.lib.pmt_cnn_bn_backward(*self._cnn_bn_common(c, hap), d_out_ptr, d_out_stride, stats.data_ptr(), gtheta, ws.data_ptr(),
+                                                 ws.numel(), _stream()), "pmt_cnn_bn_backward")
+            return
+        import torch.distributed as dist
+        ranks, rank = self._cnn_bn_ranks()
+        bn_layers = [i for i in range(c.n_layers - 1, -1, -1) if c.layers[i].kind == L.CNN_BATCHNORM]
+        for i, mom in zip(bn_layers, self._cnn_bn_exchange(c, bn_layers, ranks)):
+            own = mom.data_ptr() + rank * 3 * c.layers[i].in_ch * 8
+            L.check(self.lib.pmt_cnn_bn_backward_moments(*self._cnn_bn_common(c, hap), i, d_out_ptr, d_out_stride, stats.data_ptr(), own,
+                                                         ws.data_ptr(), ws.numel(), _stream()), "pmt_cnn_bn_backward_moments")
+            dist.all_reduce(mom, op=dist.ReduceOp.SUM, group=self.cnn_bn_group)
+            L.check(self.lib.pmt_cnn_bn_merge(C.byref(plan.desc), C.byref(c), i, n, mom.data_ptr(), ranks, rank, 1, stats.data_ptr(), gtheta,
+                                              _stream()), "pmt_cnn_bn_merge")
+        L.check(self.lib.pmt_cnn_bn_backward_full(*self._cnn_bn_common(c, hap), d_out_ptr, d_out_stride, stats.data_ptr(), gtheta, ws.data_ptr(),
+                                                  ws.numel(), _stream()),
+                "pmt_cnn_bn_backward_full")
 
     def cnn_workspace(self) -> Optional[Tensor]:
         """private rows for the haplotype CNN's weight-gradient sums (pmt_cnn_backward: workspace); PMT_CNN_WORKSPACE=0: atomics"""
@@ -440,8 +501,9 @@ class HaplotypeCnnFunction(torch.autograd.Function):
         per = engine.lib.pmt_cnn_stash_floats(C.byref(d)) if train and os.environ.get("PMT_CNN_STASH", "1") != "0" else 0
         stash = torch.empty(n * per, dtype=torch.float32, device=engine.device) if per > 0 and n > 0 else None
         ctx.bn_stats = None
-        if engine.cnn_batch_stats and n > 0:  # the BatchNorms on batch statistics: kernels of their own, no stash
-            stash = None
+        if engine.cnn_batch_stats and (n > 0 or engine.cnn_bn_sync):  # the BatchNorms on batch statistics: kernels of their own, no stash
+            stash = None                                               # (synchronised: an empty batch is refused in there)
+            ctx.bn_sync = engine.cnn_bn_sync
             ctx.bn_stats = engine.cnn_bn_forward(hap, out.data_ptr(), out.stride(0))
         else:
             if train and engine.plan.cnn_bn_folds:
@@ -464,7 +526,7 @@ class HaplotypeCnnFunction(torch.autograd.Function):
         if d_out.dtype != torch.float32 or d_out.stride(-1) != 1:
             d_out = d_out.float().contiguous()
         if ctx.bn_stats is not None:
-            eng.cnn_bn_backward(hap, d_out.data_ptr(), d_out.stride(0), ctx.bn_stats)
+            eng.cnn_bn_backward(hap, d_out.data_ptr(), d_out.stride(0), ctx.bn_stats, ctx.bn_sync)
             ctx.bn_stats = None
             return None, None, None
         ws = eng.cnn_workspace()
@@ -504,8 +566,9 @@ class VariantEmbedFunction(torch.autograd.Function):
                                      engine.plan.packed.data_ptr(), x.data_ptr(), x.stride(0), n, ve.data_ptr(), ve.stride(0),
                                      _ptr(rows_stash), engine.dropout_seed, _stream()), "pmt_rows_forward")
         ctx.bn_stats = None
-        if engine.cnn_batch_stats and n > 0:  # the BatchNorms on batch statistics: kernels of their own, no stash
-            cnn_stash = None
+        if engine.cnn_batch_stats and (n > 0 or engine.cnn_bn_sync):  # the BatchNorms on batch statistics: kernels of their own, no stash
+            cnn_stash = None                                           # (synchronised: an empty batch is refused in there)
+            ctx.bn_sync = engine.cnn_bn_sync
             ctx.bn_stats = engine.cnn_bn_forward(hap, ve.data_ptr() + 4 * e_info, ve.stride(0))
         else:
             if train and engine.plan.cnn_bn_folds:
@@ -536,7 +599,7 @@ class VariantEmbedFunction(torch.autograd.Function):
                                           rows_stash.data_ptr(), eng.space.gtheta.data_ptr(), None, 0, 1.0, _ptr(ws),
                                           0 if ws is None else ws.numel(), ctx.dropout_seed, _stream()), "pmt_rows_backward")
         if ctx.bn_stats is not None:
-            eng.cnn_bn_backward(hap, d_ve.data_ptr() + 4 * ctx.e_info, d_ve.stride(0), ctx.bn_stats)
+            eng.cnn_bn_backward(hap, d_ve.data_ptr() + 4 * ctx.e_info, d_ve.stride(0), ctx.bn_stats, ctx.bn_sync)
             ctx.bn_stats = None
             return None, None, None, None
         cws = eng.cnn_workspace()

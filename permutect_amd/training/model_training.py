@@ -132,7 +132,8 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
     model.reset_source_predictor(num_sources)
     if model._cnn_has_batchnorm():
         # the reference's `batch_norm` token trains on the statistics of the batch (calibration epochs included: they run in train mode)
-        model.train_cnn_batch_norm()
+        # under a process group on the statistics of every rank's batch: N ranks with batch B stay one process with batch N * B
+        model.train_cnn_batch_norm(sync=dist is not None)
     opt = FusedClipAdamW(model, lr=training_params.learning_rate, weight_decay=training_params.weight_decay)
     scheduler = PlateauScheduler(opt, min_lr=training_params.learning_rate / 100)
     checkpoint = Checkpoint(model, opt)
@@ -140,7 +141,9 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
     if dist is not None:
         # replicas start from rank 0's weights (reset_source_predictor drew fresh ones from every rank's own generator)
         dist.broadcast(model.engine().space.theta, src=0)
-        model.engine().params_changed()
+        for buf in model.haplotypes_cnn.buffers():  # (a BatchNorm's running statistics: outside theta; a loaded model's may differ by rank)
+            dist.broadcast(buf, src=0)
+        model.engine().params_changed()  # (also drops the eval-mode fold of the CNN, which reads those buffers)
         reduce_grads = BucketedGradAllReduce()
         model.engine().grad_hook = reduce_grads  # early bucket: reduced on a side stream under the rest of the backward
     rng = np.random.default_rng(seed + rank)
@@ -228,4 +231,6 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
     timing_log(f"epochs: {last_epoch} in {time.perf_counter() - t_epochs:.2f} s")
     if dist is not None:
         assert_replicas_identical(model.engine().space.theta)
+        for name, buf in model.haplotypes_cnn.named_buffers():  # running statistics (synchronised: the same bits everywhere) and the int64 counter
+            assert_replicas_identical(buf.double(), what=f"elements of haplotypes_cnn.{name}")
     return history
