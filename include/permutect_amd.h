@@ -313,7 +313,7 @@ int pmt_build_id(char* out, int32_t capacity);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * 0 PmtModel, 1 PmtBatch, 2 PmtOutputs, 3 PmtOutputGrads, 4 PmtAdamW, 5 PmtLinear, 6 PmtOp, 7 PmtMlp, 8 PmtBlock, 9 PmtHead,
  * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs, 16 PmtPosteriorRows,
- * 17 PmtPosteriorParams */
+ * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats */
 int pmt_struct_bytes(int which);
 
 /* Validates a descriptor against the kernels' limits. */
@@ -528,6 +528,66 @@ typedef struct PmtRecordArgs {
     const float* source_b;
 } PmtRecordArgs;
 int pmt_record_losses(const PmtRecordArgs* args, float* histograms, void* stream);
+
+/* Rank pruning of mislabeled data (reference tools/prune_dataset.py:30-164): from the artifact probabilities of ONE forward sweep, kept in
+ * device memory, the confidences, the confusion counts, the error rates, the two quantile thresholds and the list of the rows that stay.
+ * The reference sweeps the data three times and walks `.tolist()` of every batch in Python after each.
+ *   art_probs [n]: sigmoid of the capped artifact logit, row i of the dataset at i.  labels: the dataset's own Label column (0 artifact,
+ *   1 variant; every other value is unlabeled: skipped by the statistics, always kept by the selection).  CLASS 1 below is the artifact
+ *   label, class 0 the non-artifact label, as the reference's confusion matrix numbers them; a row's AGREEMENT probability is p under
+ *   an artifact label and 1 - p (fp32) under the other.
+ *   label_art_frac: artifacts / (artifacts + variants) of the label marginal (prune_dataset.py:183-186).
+ *   levels_given != 0: the quantile levels are `levels` [0 non-artifact, 1 artifact] instead of the inverse error rates, so that the
+ *   selection can be driven alone; the stages before it still run and fill the struct, and a degenerate confusion matrix is then no
+ *   refusal. */
+typedef struct PmtPruneArgs {
+    int64_t n;
+    const float* art_probs;
+    PmtIntColumn labels;
+    double label_art_frac;
+    double levels[2];
+    int32_t levels_given, reserved;
+} PmtPruneArgs;
+/* bits of PmtPruneStats.status: what the reference answers with ZeroDivisionError or torch.quantile's errors */
+#define PMT_PRUNE_NO_ARTIFACT 1         /* no row labeled artifact (or label_art_frac == 0) */
+#define PMT_PRUNE_NO_NONARTIFACT 2      /* no row labeled non-artifact (or label_art_frac == 1) */
+#define PMT_PRUNE_CONFUSION_COLUMN 4    /* a column of the confusion matrix sums to zero */
+#define PMT_PRUNE_RATES_SUM_TO_ONE 8    /* 1 - art_error_rate - nonart_error_rate == 0 */
+#define PMT_PRUNE_LEVEL_RANGE 16        /* a quantile level is NaN or outside [0, 1] */
+/* Every intermediate of the chain, index [0] the non-artifact class and [1] the artifact class throughout.  (The reference names its
+ * error rates the other way round: its `art_error_rate`, confusion[0][1] / column 1, is error_rate[1]; its `inv_art_error_rate`, the
+ * level of the ARTIFACT class's quantile, is inv_error_rate[1].) */
+typedef struct PmtPruneStats {
+    double confidence_sum[2];   /* sum of the agreement probabilities of the class (prune_dataset.py:57-58) */
+    int64_t count[2];           /* labeled rows of the class */
+    double confidence[2];       /* sum / (count + 1e-4): StreamingAverage.get, misc_utils.py:83-105 */
+    int64_t confusion[2][2];    /* [label class][1]: p >= (float)confidence[1]; [label class][0]: 1 - p >= (float)confidence[0]  (:70-91) */
+    double error_rate[2];       /* [1] = confusion[0][1] / (confusion[0][1] + confusion[1][1]), [0] = confusion[1][0] / (column 0)  (:93-94) */
+    double inv_error_rate[2];   /* the quantile levels (:100-109, or `levels`) */
+    float threshold[2];         /* quantile of the class's agreement probabilities at its level (:120-121); NaN when status != 0 */
+    int32_t status, reserved;
+} PmtPruneStats;
+/* Bytes of the scratch buffer both calls below take for n rows (any alignment of 8).  Its contents mean nothing between calls. */
+size_t pmt_prune_scratch_bytes(int64_t n);
+/* `calculate_pruning_thresholds` (prune_dataset.py:30-129) in one call of nine short launches (behind two memsets) on `stream`, each reading what the one
+ * before left in device memory; nothing waits for the device and no workgroup waits for another.  Sums: the agreement probabilities in
+ * double, a partial per workgroup folded in workgroup order.  Counts and histograms: integer atomics.  So run-to-run bit-identical.
+ * The quantiles are exact order statistics by radix selection on the bits of the agreement probability (a non-negative float orders as
+ * its bit pattern), 8 bits a pass, both classes and both neighbours floor(rank), ceil(rank) in the same four passes, and then ATen's
+ * arithmetic (aten/src/ATen/native/Sorting.cpp quantile_compute, Lerp.h): the level rounded to fp32, rank = level * (count - 1) in fp32,
+ * weight = rank - floor(rank), lerp = weight < 0.5 ? fma(weight, hi - lo, lo) : fma(-(hi - lo), 1 - weight, hi) -- bit for bit
+ * torch.quantile's answer on the CPU for a class of up to 2^24 rows; beyond that, where torch refuses, rank and weight in double and
+ * lo + weight * (hi - lo) in double, rounded once.
+ * `stats` (device) is written whole.  A degenerate input sets `status` and leaves both thresholds NaN; nothing is divided by zero and
+ * no rank is looked up.  n == 0: PMT_OK, status = NO_ARTIFACT | NO_NONARTIFACT | CONFUSION_COLUMN.  A NULL struct, stats or scratch, n < 0, art_probs or
+ * labels NULL with n > 0, or a label width other than 4 or 8: PMT_E_INVALID, nothing launched. */
+int pmt_prune_thresholds(const PmtPruneArgs* args, PmtPruneStats* stats, void* scratch, void* stream);
+/* `generated_pruned_data_for_fold`'s rule (prune_dataset.py:133-164) over all n rows: a row goes iff it is labeled artifact and
+ * p < art_threshold, or labeled non-artifact and 1 - p < nonart_threshold (fp32).  The rows that stay, as ascending int64 indices, into
+ * kept_ids [n] and their number into *kept_count (device): an ordered stream compaction in three launches (count per workgroup, scan,
+ * scatter).  NaN thresholds keep everything; `levels`, `label_art_frac` are not read.  n == 0: *kept_count = 0. */
+int pmt_prune_select(const PmtPruneArgs* args, float art_threshold, float nonart_threshold, int64_t* kept_ids, int64_t* kept_count,
+                     void* scratch, void* stream);
 
 /* The tallies of an evaluation step (reference metrics/evaluation_metrics.py:49-66 -> AccuracyMetrics, metrics/loss_metrics.py:226-243;
  * training/model_training.py:204-228 runs it three times per parent batch after every validation epoch): the weights of the LABELED

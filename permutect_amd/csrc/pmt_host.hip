@@ -42,6 +42,8 @@ extern "C" int pmt_struct_bytes(int which) {
         case 15: return (int)sizeof(PmtEvalArgs);
         case 16: return (int)sizeof(PmtPosteriorRows);
         case 17: return (int)sizeof(PmtPosteriorParams);
+        case 18: return (int)sizeof(PmtPruneArgs);
+        case 19: return (int)sizeof(PmtPruneStats);
         default: return PMT_E_INVALID;
     }
 }

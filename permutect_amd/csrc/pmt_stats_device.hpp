@@ -1,4 +1,4 @@
-// What the statistical kernels share (pmt_downsample_fit.hip, pmt_spectra_fit.hip, pmt_posterior.hip): torch.optim.Adam's update and
+// What the statistical kernels share (pmt_downsample_fit.hip, pmt_spectra_fit.hip, pmt_posterior.hip, pmt_prune.hip): torch.optim.Adam's update and
 // its bias corrections, the sums over a wavefront, the fp32 digamma and the beta-binomial.  One definition each: the fits are pinned
 // by trajectory against float64 references, so a change here reaches all of them or none.  Every expression keeps its written order
 // of operations (plain fp32 / double, IEEE division and square root).
@@ -64,6 +64,12 @@ __device__ __forceinline__ float fit_sum32(float x) {
 __device__ __forceinline__ float fit_sum64(float x) {
     x = fit_sum16(x);
     return (fit_lane(x, 0) + fit_lane(x, 16)) + (fit_lane(x, 32) + fit_lane(x, 48));
+}
+
+// the same in double (pmt_prune.hip): an xor butterfly, whose two addends at every level are the same pair in both lanes
+__device__ __forceinline__ double fit_sum64(double x) {
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
+    return x;
 }
 
 // The bias corrections of a persistent fit: lane j holds those of step (t & ~63) + j + 1, computed once every 64 steps, and step t

@@ -91,7 +91,10 @@ class MemoryMappedData:
         """A new dataset holding only the given folds, in order (reference :90-106; a vectorised copy here)."""
         if used_folds is None:
             return self
-        keep = self.fold_indices(num_folds, used_folds)
+        return self.take(self.fold_indices(num_folds, used_folds))
+
+    def take(self, keep: np.ndarray) -> "MemoryMappedData":
+        """A new dataset holding the data `keep` (int64 indices) in that order, each with its reads: one gather per array."""
         starts = self.read_start_indices()
         if self.reads_mmap is None:
             reads = None

@@ -157,6 +157,10 @@ class ReadsDataset:
             self._totals_slvra = torch.from_numpy(total.astype(np.float32)).view(shape)
         return self._totals_slvra
 
+    def labels(self) -> np.ndarray:
+        """the Label of every datum (int16 [len(self)], a view of the integer table's column)"""
+        return np.asarray(self._ints[: self._size, Data.LABEL.idx])
+
     def num_read_features(self) -> int:
         nb = NUMBER_OF_BYTES_IN_PACKED_READ
         if self._reads is None:  # a dataset without reads (the posterior hand-off)
