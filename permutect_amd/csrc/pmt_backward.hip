@@ -390,7 +390,7 @@ DEV void backward_group(
         trace_ev(c, 14);
         unsigned long long t_rot = prof_now();
         // ---- rotation + translation backward: a = Q (e + t) ------------------------------------------------------------
-        linear_wgrad<NTE, NTE, BFB>(c, R, da, e);
+        linear_wgrad<NTE, NTE, BFB, S::DIM_E ? PMT_BC_NONE : PMT_BC_ONES>(c, R, da, e);  // (Q has no bias: the exact-width instances sum none)
         f4 de[PMT_RT][NTE];
         init_bias<NTE>(de, nullptr, E, g);
         if constexpr (S::BF16) linear_acc_bf16<NTE, NTE, false, PMT_DG(BFB)>(de, da, packed + uniform(R.wtb_frag));
@@ -592,7 +592,7 @@ DEV void backward_group(
             trace_ev(c, 19);
             t_ph = prof_now();
             // proj2 weight gradients of both sides in one exchange round
-            if constexpr (S::BF16 != 0) wgrad_exchange_bf<NTD, HT, 2, BFB>(c, M->lin[uniform(B.proj2[0])], M->lin[uniform(B.proj2[1])], dy, u, 1.0f);
+            if constexpr (S::BF16 != 0) wgrad_exchange_bf<NTD, HT, 2, BFB, PMT_BC_OF(S::DIM_H)>(c, M->lin[uniform(B.proj2[0])], M->lin[uniform(B.proj2[1])], dy, u, 1.0f);
             else wgrad_exchange<NTD, HT, 2>(c, M->lin[uniform(B.proj2[0])], M->lin[uniform(B.proj2[1])], dy, u, 1.0f);
         }
         if (c.dbg & 1) __syncthreads();  // (the exchange's barriers, skipped by that switch, complete gsum)
@@ -729,7 +729,7 @@ DEV void backward_group(
             f4 n[PMT_RT][NTD];
             if (!xh4_requested) load_xh4();  // (the generic instances and the later slices of a layered backward: no early request)
             affine_n(n, xh4);
-            if constexpr (S::BF16 != 0) wgrad_exchange_bf<2 * HT, NTD, 2, BFB>(c, M->lin[uniform(B.proj1[0])], M->lin[uniform(B.proj1[1])], dz, n, 1.0f);
+            if constexpr (S::BF16 != 0) wgrad_exchange_bf<2 * HT, NTD, 2, BFB, PMT_BC_OF(S::DIM_D)>(c, M->lin[uniform(B.proj1[0])], M->lin[uniform(B.proj1[1])], dz, n, 1.0f);
             else wgrad_exchange<2 * HT, NTD, 2>(c, M->lin[uniform(B.proj1[0])], M->lin[uniform(B.proj1[1])], dz, n, 1.0f);
         }
         prof_add(c, 13, t_ph);

@@ -646,9 +646,23 @@ DEV void stage_pair_bf16(char* const (&pj)[4], int off, f4 v0, f4 v1) {
 
 #define PMT_BF_PLANE_BYTES 2048  // hi + mid piece of one (wave, plane)
 #define PMT_ABL(c, bit) (PMT_BWD_ABLATE && ((c).dbg & (bit)))
-template <int NTO, int NTI, int SIDES, int BF = 3>
+// Where the bias gradient of a linear comes from (BC of wgrad_exchange_bf).
+// PMT_BC_ONES: every block multiplies its dy operand once more against a plane of ones and the one block per output row that owns the
+//   bias emits the row sums through the table's bias tail (the run-time-width instance; a width that fills its last tile).
+// BC >= 0, the linear's input width, known at compile time and no multiple of 16: the staged x plane holds 1.0 at feature position BC --
+//   a padding position of a plane that is staged and contracted anyway -- so column BC of dW IS the bias gradient (am . 1 + ah . 0 + ah . 1:
+//   the very terms of the ones products, in their order), and pmt_pack_kernel points that column's table entries at the bias.  No second
+//   accumulator, no second table row, no bias branch in either emit path.  The x registers themselves stay as they are.
+// PMT_BC_NONE: a linear without a bias (the rotation).
+#define PMT_BC_ONES (-1)
+#define PMT_BC_NONE (-2)
+// the bias column of a linear of compile-time input width WI (0: known at run time only) in an instance with the bf16 exchange
+#define PMT_BC_OF(WI) (((WI) > 0 && ((WI) & 15) != 0) ? (WI) : PMT_BC_ONES)
+template <int NTO, int NTI, int SIDES, int BF = 3, int BC = PMT_BC_ONES>
 DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, const f4 (&dy)[PMT_RT][NTO],
                            const f4 (&x)[PMT_RT][NTI], float scale) {
+    static_assert(BC < 16 * NTI, "the bias column lies in the padding of the last input tile");
+    constexpr bool ONES = BC == PMT_BC_ONES;
     static_assert(PMT_RT == 2 && NTO > 0, "a wave's two tiles are the 32 reads of one MFMA");  // (checked where it is instantiated: pmt_cnn2.hip includes this header with one tile per wave)
     if (c.dbg & 1) return;
     constexpr int PIECES = PMT_BF_PIECES(BF);
@@ -670,10 +684,11 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
     const int lane = pmt_tid() & 63, g = lane >> 4, wave = uniform((int)(pmt_tid() >> 6));
     const int my_slot = wave, wr_s = c.wr;
     int t_ot[TPW], t_it[TPW], t_side[TPW];
-    f4 acc[TPW], accb[TPW];
+    f4 acc[TPW], accb[ONES ? TPW : 1];
 #pragma unroll
     for (int k = 0; k < TPW; ++k) {
-        acc[k] = accb[k] = f4{0.f, 0.f, 0.f, 0.f};
+        acc[k] = f4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (ONES) accb[k] = acc[k];
         if (COLS) {
             t_it[k] = wave % NTI;
             t_ot[k] = wave / NTI + ROWS * k;
@@ -690,19 +705,21 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
     const bf8 ones = __builtin_bit_cast(bf8, u4v{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});  // 1.0 everywhere
     // destinations of this wave's blocks (PmtLinear.emit_tab), fetched now: the loads are long back when the sums are ready
     typedef int i4 __attribute__((ext_vector_type(4)));
-    i4 e[TPW], eb[TPW];
-    bool with_bias[TPW];
+    i4 e[TPW], eb[ONES ? TPW : 1];
+    bool with_bias[ONES ? TPW : 1];
 #pragma unroll
     for (int k = 0; k < TPW; ++k) {
-        e[k] = eb[k] = i4{-1, -1, -1, -1};
-        with_bias[k] = false;
+        e[k] = i4{-1, -1, -1, -1};
+        if constexpr (ONES) { eb[k] = e[k]; with_bias[k] = false; }
         if (!ALL_TASKS && t_side[k] < 0) continue;
         const PmtLinear& L = (SIDES == 2 && t_side[k] == 1) ? L1 : L0;
         // (private partial sums: the same 16 bytes are this lane's running sums of the block instead of its destinations)
         const int* tab = reinterpret_cast<const int*>(PRIV ? c.priv + uniform(L.emit_tab) : c.packed + uniform(L.emit_tab));
         e[k] = *reinterpret_cast<const i4*>(tab + ((t_ot[k] * NTI + t_it[k]) * 64 + lane) * 4);
-        with_bias[k] = t_it[k] == t_ot[k] % NTI;  // the one block of row ot that also sums the bias gradient (dy x ones)
-        if (with_bias[k]) eb[k] = *reinterpret_cast<const i4*>(tab + NB * 256 + t_ot[k] * 16 + 4 * g);
+        if constexpr (ONES) {
+            with_bias[k] = t_it[k] == t_ot[k] % NTI;  // the one block of row ot that also sums the bias gradient (dy x ones)
+            if (with_bias[k]) eb[k] = *reinterpret_cast<const i4*>(tab + NB * 256 + t_ot[k] * 16 + 4 * g);
+        }
     }
     char* stage = reinterpret_cast<char*>(c.stage);
     unsigned long long t0c = prof_now();
@@ -724,7 +741,16 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
 #pragma unroll
             for (int ot = 0; ot < NTO; ++ot) stage_pair_bf16<PIECES>(pj, ot * PMT_BF_PLANE_BYTES, dy[0][ot], dy[PMT_RT - 1][ot]);
 #pragma unroll
-            for (int it = 0; it < NTI; ++it) stage_pair_bf16<PIECES>(pj, (NTO + it) * PMT_BF_PLANE_BYTES, x[0][it], x[PMT_RT - 1][it]);
+            for (int it = 0; it < NTI; ++it) {
+                f4 x0 = x[0][it], x1 = x[PMT_RT - 1][it];
+                if constexpr (BC >= 0) {
+                    if (it == (BC >> 4)) {  // feature BC = register (BC & 15) >> 2 of the lanes of group BC & 3: the bias column (copies: x itself stays)
+                        x0[(BC & 15) >> 2] = g == (BC & 3) ? 1.0f : x0[(BC & 15) >> 2];
+                        x1[(BC & 15) >> 2] = g == (BC & 3) ? 1.0f : x1[(BC & 15) >> 2];
+                    }
+                }
+                stage_pair_bf16<PIECES>(pj, (NTO + it) * PMT_BF_PLANE_BYTES, x0, x1);
+            }
         }
         prof_add(c, 18, t1);
         t1 = prof_now();
@@ -751,10 +777,10 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
                         if constexpr (PIECES != 1) {
                             acc[k] = mfma_bf16(am, bh, acc[k]);
                             acc[k] = mfma_bf16(ah, bm, acc[k]);
-                            accb[k] = mfma_bf16(am, ones, accb[k]);
+                            if constexpr (ONES) accb[k] = mfma_bf16(am, ones, accb[k]);
                         }
                         acc[k] = mfma_bf16(ah, bh, acc[k]);
-                        accb[k] = mfma_bf16(ah, ones, accb[k]);
+                        if constexpr (ONES) accb[k] = mfma_bf16(ah, ones, accb[k]);
                     }
                 }
             }
@@ -773,15 +799,15 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
                     if constexpr (PIECES != 1) {
                         acc[k] = mfma_bf16(am, bh, acc[k]);
                         acc[k] = mfma_bf16(ah, bm, acc[k]);
-                        accb[k] = mfma_bf16(am, ones, accb[k]);
+                        if constexpr (ONES) accb[k] = mfma_bf16(am, ones, accb[k]);
                     }
                     acc[k] = mfma_bf16(ah, bh, acc[k]);
-                    accb[k] = mfma_bf16(ah, ones, accb[k]);
+                    if constexpr (ONES) accb[k] = mfma_bf16(ah, ones, accb[k]);
                 }
             }
         }
-        // (bias gradients = the row sums of dy: EVERY block multiplies its A operand once more against a plane of ones -- the matrix pipe has
-        //  the room -- and the one block per row that owns the bias emits them: no second pass over the stage by half the waves)
+        // (ONES: bias gradients = the row sums of dy: EVERY block multiplies its A operand once more against a plane of ones and the one
+        //  block per row that owns the bias emits them: no second pass over the stage by half the waves)
     }
     prof_add(c, 0, t0c);
     trace_ev(c, 104);
@@ -797,8 +823,10 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
             const PmtLinear& L = side1 ? L1 : L0;
             float* row = c.priv + uniform(L.emit_tab);
             *reinterpret_cast<f4*>(row + ((t_ot[k] * NTI + t_it[k]) * 64 + lane) * 4) = __builtin_bit_cast(f4, e[k]) + scale * acc[k];
-            if (with_bias[k] && (lane & 15) == 0)
-                *reinterpret_cast<f4*>(row + NB * 256 + t_ot[k] * 16 + 4 * g) = __builtin_bit_cast(f4, eb[k]) + scale * accb[k];
+            if constexpr (ONES) {
+                if (with_bias[k] && (lane & 15) == 0)
+                    *reinterpret_cast<f4*>(row + NB * 256 + t_ot[k] * 16 + 4 * g) = __builtin_bit_cast(f4, eb[k]) + scale * accb[k];
+            }
         }
     } else {  // four atomics per block at the tabulated offsets; no index arithmetic here
 #pragma unroll
@@ -811,10 +839,12 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (e[k][j] >= 0) atomicAdd(gw + e[k][j], scale * acc[k][j]);
-            if (with_bias[k] && (lane & 15) == 0) {  // every column of accb holds the row sums: the lanes of column 0 add them
+            if constexpr (ONES) {
+                if (with_bias[k] && (lane & 15) == 0) {  // every column of accb holds the row sums: the lanes of column 0 add them
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (eb[k][j] >= 0) atomicAdd(c.gtheta + eb[k][j], scale * accb[k][j]);
+                    for (int j = 0; j < 4; ++j)
+                        if (eb[k][j] >= 0) atomicAdd(c.gtheta + eb[k][j], scale * accb[k][j]);
+                }
             }
         }
     }
@@ -822,10 +852,10 @@ DEV void wgrad_exchange_bf(BwdCtx& c, const PmtLinear& L0, const PmtLinear& L1, 
     trace_ev(c, 105);
 }
 
-template <int NTO, int NTI, int BF = 0>
+template <int NTO, int NTI, int BF = 0, int BC = PMT_BC_ONES>
 DEV void linear_wgrad(BwdCtx& c, const PmtLinear& L, const f4 (&dy)[PMT_RT][NTO], const f4 (&x)[PMT_RT][NTI],
                       float scale = 1.0f) {
-    if constexpr (BF != 0) wgrad_exchange_bf<NTO, NTI, 1, BF>(c, L, L, dy, x, scale);
+    if constexpr (BF != 0) wgrad_exchange_bf<NTO, NTI, 1, BF, BC>(c, L, L, dy, x, scale);
     else wgrad_exchange<NTO, NTI, 1>(c, L, L, dy, x, scale);
 }
 
@@ -849,7 +879,7 @@ DEV void linear_op_backward(BwdCtx& c, const PmtOp& o, f4 (&dy)[PMT_RT][NTO], co
             for (int t = 0; t < NTO; ++t) dy[rt][t] = selu_bwd4(dy[rt][t], selu4(y[rt][t]));
     }
     if (dropping) drop_apply<NTO>(*c.drop, uniform(o.lin[0]), dy, c.g);
-    linear_wgrad<NTO, NTI, BF>(c, L, dy, x);
+    linear_wgrad<NTO, NTI, BF, PMT_BC_OF(WI)>(c, L, dy, x);
     if (want_dx) {
         init_bias<NTI>(dx, nullptr, in_dim, c.g);
         if constexpr (BF) linear_acc_bf16<NTO, NTI, false, PMT_DG(BF)>(dx, dy, c.packed + uniform(L.wtb_frag));
@@ -960,7 +990,7 @@ DEV void mlp_backward(BwdCtx& c, const PmtMlp& mlp, f4 (&dy)[PMT_RT][NT], bool n
                     for (int t = 0; t < NT; ++t) dy[rt][t] = selu_bwd4(dy[rt][t], selu4(y[rt][t]));
             }
             if (dropping) drop_apply<NT>(*c.drop, uniform(o.lin[0]), dy, c.g);  // d(Wx + b) = mask * d(masked)
-            linear_wgrad<NT, NT, BF>(c, L, dy, x);
+            linear_wgrad<NT, NT, BF, PMT_BC_OF(W)>(c, L, dy, x);
             if (op > op_begin || need_input_grad) {
                 f4 dx[PMT_RT][NT];
                 init_bias<NT>(dx, nullptr, in_dim, c.g);
@@ -1004,7 +1034,7 @@ DEV void mlp_backward(BwdCtx& c, const PmtMlp& mlp, f4 (&dy)[PMT_RT][NT], bool n
             // dyl: the gradient w.r.t. the last Linear's own output (per unit of alpha) -- dy itself, or with dropout mask2 * dy
             // (a copy: dy is still needed whole for the residual path)
             auto last_layer = [&](const f4 (&dyl)[PMT_RT][NT]) {
-                linear_wgrad<NT, NT, BF>(c, L2, dyl, s1, alpha);
+                linear_wgrad<NT, NT, BF, PMT_BC_OF(W)>(c, L2, dyl, s1, alpha);
                 init_bias<NT>(d1, nullptr, width, c.g);
                 if constexpr (BF) linear_acc_bf16<NT, NT, false, PMT_DG(BF)>(d1, dyl, c.packed + uniform(L2.wtb_frag));
                 else linear_acc<NT, NT, false, EXACT, W>(d1, dyl, c.packed + uniform(L2.wt_frag), width, width);
@@ -1048,7 +1078,7 @@ DEV void mlp_backward(BwdCtx& c, const PmtMlp& mlp, f4 (&dy)[PMT_RT][NT], bool n
 #pragma unroll
                     for (int t = 0; t < NT; ++t) s0[rt][t] = selu4(s0[rt][t]);
                 trace_ev(c, 222);
-                linear_wgrad<NT, NT, BF>(c, L1, d1, s0);
+                linear_wgrad<NT, NT, BF, PMT_BC_OF(W)>(c, L1, d1, s0);
                 f4 d0[PMT_RT][NT];
                 init_bias<NT>(d0, nullptr, width, c.g);
                 if constexpr (BF) linear_acc_bf16<NT, NT, false, PMT_DG(BF)>(d0, d1, c.packed + uniform(L1.wtb_frag));

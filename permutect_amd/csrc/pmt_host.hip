@@ -651,8 +651,10 @@ DEV int split_row(int v, int h) {
 // one job per workgroup: (lin, 0) forward frags, (lin, 1) transposed frags, (lin, 2) bias, (lin, 3 / 4) the same two matrices
 // as bf16 pieces, (lin, 5) the weight-gradient emit table, (lin, 6) the forward matrix as two f16 pieces, then per-block vectors
 #define PMT_PACK_KINDS 7
+// bias_cols: the model runs the exact-width instances of the read-set backward (pmt_shape_id 2 / 3), whose weight-gradient exchange sums
+// a bias gradient in the padding column in_dim of dW (pmt_bwd_device.hpp: PMT_BC_OF)
 __global__ void pmt_pack_kernel(const PmtModel* __restrict__ M, const float* __restrict__ theta,
-                                const float* __restrict__ phi, float* __restrict__ packed) {
+                                const float* __restrict__ phi, float* __restrict__ packed, int bias_cols) {
     const int job = blockIdx.x;
     const int n_lin_jobs = M->n_linear * PMT_PACK_KINDS;
     if (job < n_lin_jobs) {
@@ -668,17 +670,23 @@ __global__ void pmt_pack_kernel(const PmtModel* __restrict__ M, const float* __r
             int* tab = reinterpret_cast<int*>(packed + L.emit_tab);
             const int nmt = (out_v + 15) >> 4, nkt = (L.in_dim + 15) >> 4;
             const int w_off = L.w_src >= 0 ? L.w_src : -(L.w_src + 2);
+            // A width that leaves padding in its last input tile, in a model of the exact-width instances: column in_dim of row o is the
+            // bias gradient of row o (the kernel stages 1.0 at that position of x) and the bias tail stays empty.  The column lands in
+            // the buffer of the weights, so a bias that lives elsewhere has no destination (as in the tail).
+            const bool bias_col = bias_cols != 0 && (L.in_dim & 15) != 0;
+            const bool bias_same = L.w_src >= 0 && L.b_src >= 0;
             for (int i = threadIdx.x; i < nmt * nkt * 256; i += blockDim.x) {
                 const int j = i & 3, lane = (i >> 2) & 63, blk = i >> 8;
                 const int ot = blk / nkt, it = blk - ot * nkt;
                 const int pf = 16 * ot + 4 * j + (lane >> 4), o = pf < out_v ? split_row(pf, h) : -1;
                 const int cp = lane & 15, col = 16 * it + 4 * (cp & 3) + (cp >> 2);
-                tab[i] = (o >= 0 && o < L.out_dim && col < L.in_dim) ? w_off + o * L.in_dim + col : -1;
+                tab[i] = (o >= 0 && o < L.out_dim && col < L.in_dim) ? w_off + o * L.in_dim + col
+                         : (bias_col && bias_same && o >= 0 && o < L.out_dim && col == L.in_dim) ? L.b_src + o : -1;
             }
             int* btab = tab + nmt * nkt * 256;
             for (int i = threadIdx.x; i < nmt * 16; i += blockDim.x) {
                 const int p = i & 15, pf = 16 * (i >> 4) + 4 * (p & 3) + (p >> 2), o = pf < out_v ? split_row(pf, h) : -1;
-                btab[i] = (L.b_src >= 0 && o >= 0 && o < L.out_dim) ? L.b_src + o : -1;
+                btab[i] = (!bias_col && L.b_src >= 0 && o >= 0 && o < L.out_dim) ? L.b_src + o : -1;
             }
             return;
         }
@@ -809,8 +817,9 @@ extern "C" int pmt_pack_params(const PmtModel* model_host, const PmtModel* model
     const int rc = pmt_model_check(model_host);
     if (rc) return rc;
     const int jobs = model_host->n_linear * PMT_PACK_KINDS + model_host->num_blocks * 5 + 1;
+    const int shape = pmt_shape_id(model_host);
     hipLaunchKernelGGL(pmt_pack_kernel, dim3(jobs), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), model_dev, theta,
-                       phi, packed);
+                       phi, packed, (shape == 2 || shape == 3) ? 1 : 0);
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
 }
 
