@@ -297,6 +297,18 @@ int pmt_abi_version(void);
  * through force_shape only), 6 the build's tiles on the 16-bit matrix pipes with the widths read at run time, 2 the build's widths
  * compiled in, 3 the same with plain bf16 products.  Replaces nothing in the reference: its ATen kernels take any width
  * (architecture/mlp.py:32-67, parameters.py:70-156). */
+#define PMT_SHAPE_ANY 0            /* generic: any supported model, fp32 MFMAs, every tile guarded                                    */
+#define PMT_SHAPE_TILES_F32 1      /* the build's tile counts, widths at run time, fp32 MFMAs (PMT_FORCE_TILES_F32, split read sets)  */
+#define PMT_SHAPE_EXACT 2          /* the build's widths compiled in, fp32-equivalent products on the 16-bit matrix pipes             */
+#define PMT_SHAPE_EXACT_BF16 3     /* the same widths with plain bf16 products (PMT_FORCE_EXACT_BF16; not a parity mode)              */
+#define PMT_SHAPE_EXACT_DROPOUT 4  /* PMT_SHAPE_EXACT carrying a training step's dropout masks (chosen per batch, never by pmt_shape_id) */
+#define PMT_SHAPE_TILES 6          /* the build's tile counts, widths at run time, on the 16-bit matrix pipes                         */
+/* PmtModel.force_shape */
+#define PMT_FORCE_AUTO 0
+#define PMT_FORCE_TILES_F32 1      /* at most PMT_SHAPE_TILES_F32                                    */
+#define PMT_FORCE_ANY 2            /* PMT_SHAPE_ANY                                                  */
+#define PMT_FORCE_EXACT_BF16 3     /* PMT_SHAPE_EXACT_BF16 where PMT_SHAPE_EXACT applies             */
+#define PMT_FORCE_FWD_BF16X3 5     /* the exact-width FORWARD on three bf16 pieces; auto otherwise   */
 int pmt_shape_info(int32_t* nine);
 int pmt_shape_id(const struct PmtModel* m);
 /* The compile-time limits of THIS build of the library: four[0] widest register-resident activation (PMT_MAX_WIDTH: 64; the wide

@@ -19,28 +19,13 @@
 #define PMT_WAVES PMT_GROUP_WAVES
 #define PMT_RT 2
 #define PMT_BWD_WAVES_PER_SIMD 2
-#ifndef PMT_BWD_PIECES
-#define PMT_BWD_PIECES 3  // pieces of the products that keep the forward's precision (the head's recomputation); the input-gradient and
-                          // recomputation products of the layers take PMT_DGRAD_PIECES / PMT_RECOMPUTE_PIECES (pmt_bwd_device.hpp)
-#endif
+// pieces of the products that keep the forward's precision (the head's recomputation); the input-gradient and recomputation products of
+// the layers take PMT_DGRAD_PIECES / PMT_RECOMPUTE_PIECES (pmt_bwd_device.hpp)
+constexpr int BWD_HEAD_PIECES = 3;
 #include "permutect_amd.h"
 #define PMT_STAGE_PLANES ((16 - 2 * (PMT_MAX_HALF_FFN / 16 - 1)) * PMT_GROUP_WAVES)  // every wave's operands of a 4 + 4 tile linear at once (8 waves x 8 planes x (hi + mid)); a build with two-tile gate halves gives 16 KiB of it to the wider per-set tables
-#include "permutect_amd.h"
 #define PMT_OPAQUE_TID 1  // the kernel loops over groups (persistent launch): see pmt_tid
-#ifndef PMT_BWD_XH4_AT_P3
-#define PMT_BWD_XH4_AT_P3 0  // where phase 4's stash read of xhat_l is requested: 0 in phase 4 itself; 1 / 2 in phase 3 (round 2: 2.94 -> 3.04 ms: the
-                             // in-order memory counter makes the phase's small loads wait for it); 3 together with z in phase 1, pinned by
-                             // scheduling barriers (round 5, on the kernel with run-time debug branches: 2.42 -> 2.39 ms).  Measured again on the
-                             // kernel WITHOUT those branches (the scheduler now moves loads across whole phases by itself): 0 / 2: 2.03 - 2.04 ms,
-                             // 3: 2.06, 1: 2.09 -- the 32 registers an early request holds cost more than the overlap gives; back to 0
-#endif
-#ifndef PMT_BWD_PRIO
-#define PMT_BWD_PRIO 0
-#endif
-#ifndef PMT_BWD_FRAG_AHEAD
-#define PMT_BWD_FRAG_AHEAD 6
-#endif
-#define PMT_FRAG_AHEAD PMT_BWD_FRAG_AHEAD  // weight fragments six MFMA groups ahead (2 waves per SIMD do not hide an L2 round trip): 0 -> 1: 3.59 -> 3.52 ms; 1 -> 3: 3.31 -> 3.27 ms; round 4, 3 -> 6: 2.43 -> 2.40 ms (8: the same)
+#define PMT_FRAG_AHEAD 6  // weight fragments six MFMA groups ahead (2 waves per SIMD do not hide an L2 round trip): 0 -> 1: 3.59 -> 3.52 ms; 1 -> 3: 3.31 -> 3.27 ms; round 4, 3 -> 6: 2.43 -> 2.40 ms (8: the same)
 #include "pmt_device.hpp"
 #include "pmt_mlp_device.hpp"
 #include "pmt_bwd_device.hpp"
@@ -102,9 +87,6 @@ DEV void load_slot_tiles(const float* const (&stash_tile)[PMT_RT], unsigned mask
 // Layered execution (pmt_backward_layered; read sets split over several workgroups): launch `slice` finishes block
 // L - slice from the COMPLETE per-set sums of d(gate) and starts block L - slice - 1; the sums accumulate in HBM, the
 // running gradient and the half-finished block's per-read state rest in scratch between launches.
-#ifndef PMT_BWD_Z_F16
-#define PMT_BWD_Z_F16 1
-#endif
 #define PMT_BWD_PARK_TILES (5 * PMT_HT + 1)  // z1, z2, z2hat, d(gate), d(u) (PMT_HT tiles each) and the rstd of LayerNorm(h)
 struct PmtBwdLayered {
     int slice;
@@ -131,7 +113,7 @@ DEV void backward_group(
     // Pieces of the activations / gradients in the backward's products: BFB (three, like the forward) where PMT_DG / PMT_RC do not
     // apply; the layers' input-gradient and recomputation products run on two (pmt_bwd_device.hpp, with the fp64 yardstick).
     // BFP: the pieces, for the products called from here; BFB: the same + the PRIV bit, for everything that reaches an exchange.
-    constexpr int BFP = S::BF16 == 3 ? PMT_BWD_PIECES : S::BF16;
+    constexpr int BFP = S::BF16 == 3 ? BWD_HEAD_PIECES : S::BF16;
     constexpr int BFB = BFP | ((PRIV && S::BF16 != 0) ? PMT_BF_PRIV : 0);
     static_assert(!PRIV || S::BF16 != 0, "private rows: the bf16-exchange instances only (priv_kernel picks)");
     static_assert(EX || (NTF == NTD && NTR == NTD && NTE == NTD), "the generic shape keeps one array width");
@@ -460,9 +442,11 @@ DEV void backward_group(
                 for (int rt = 0; rt < PMT_RT; ++rt) n[rt][t] = xh[rt][t] * lw + lb;
             }
         };
-        f4 xh4[PMT_RT][NTD];  // phase 4's xhat_l and rstd
+        // phase 4's xhat_l and rstd, requested in phase 4 itself: requested earlier (with z in phase 1, or in phase 3) the 32 registers they
+        // hold cost more than the overlap gives (2.03 - 2.04 ms here; 2.06 - 2.09).  Declared up here and loaded through a lambda because
+        // the compiler's schedule of the whole kernel depends on both: either one moved into phase 4 changes the kernel's code.
+        f4 xh4[PMT_RT][NTD];
         float rs4[PMT_RT];
-        bool xh4_requested = false;
         auto load_xh4 = [&]() {
             load_xhat(xh4, l);
 #pragma unroll
@@ -477,18 +461,10 @@ DEV void backward_group(
         constexpr int PARK = 5 * HT + 1;  // tiles a layered launch parks per read tile (PMT_BWD_PARK_TILES)
         f4 z[PMT_RT][2 * HT];
         if (first_half) {
-            if constexpr (EX && PMT_STASH_Z) {
+            if constexpr (EX) {
 #pragma unroll
                 for (int rt = 0; rt < PMT_RT; ++rt) {
                     stash_load<2 * HT>(stash_tile[rt] + (size_t)(slot_z0 + l) * PMT_SLOT_FLOATS, z[rt]);
-                }
-                // (3: phase 4's xhat_l requested TOGETHER with z -- the two HBM round trips of a block overlap instead of following each
-                //  other; the 32 registers it holds through phases 2 - 3 are paid for with a shallower fragment prefetch)
-                if (PMT_BWD_XH4_AT_P3 == 3) {
-                    __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise sinks the request down to its use)
-                    load_xh4();
-                    __builtin_amdgcn_sched_barrier(0);
-                    xh4_requested = true;
                 }
             } else {
                 f4 n[PMT_RT][NTD], xq[PMT_RT][NTD];
@@ -500,10 +476,8 @@ DEV void backward_group(
 #pragma unroll
                     for (int rt = 0; rt < PMT_RT; ++rt) z[rt][t] = b_t;
                 }
-                // (the gate multiplies by this: fp32-equivalent products -- three f16 MFMAs on two-piece splits like the forward's, or
-                //  with PMT_BWD_Z_F16 = 0 the six bf16 MFMAs on three-piece splits of round 3)
-                if constexpr (S::BF16 && PMT_BWD_Z_F16) linear_acc_f16<NTD, 2 * HT, false>(z, n, packed + uniform(P1.wh_frag));
-                else if constexpr (S::BF16) linear_acc_bf16<NTD, 2 * HT, false, BFP>(z, n, packed + uniform(P1.wb_frag));
+                // (the gate multiplies by this: fp32-equivalent products -- three f16 MFMAs on two-piece splits like the forward's)
+                if constexpr (S::BF16) linear_acc_f16<NTD, 2 * HT, false>(z, n, packed + uniform(P1.wh_frag));
                 else linear_acc<NTD, 2 * HT, false, EX, S::DIM_D>(z, n, packed + uniform(P1.w_frag), D, PMT_SPLIT0 + h);
 #pragma unroll
                 for (int rt = 0; rt < PMT_RT; ++rt)
@@ -685,7 +659,6 @@ DEV void backward_group(
         trace_ev(c, 21);
         t_ph = prof_now();
         // ---- phase 3: finish d(z2), LayerNorm(h) backward, SELU backward -> d(zpre) ---------------------------------------
-        if (PMT_BWD_XH4_AT_P3 == 1) { load_xh4(); xh4_requested = true; }  // phase 4's stash read, requested here: phase 3 is ~3.6 k cycles of arithmetic to hide it under
         f4 dz[PMT_RT][2 * HT];
         {
             f4 dsw[HT], dsb[HT];
@@ -711,12 +684,6 @@ DEV void backward_group(
 #pragma unroll
                 for (int t = 0; t < HT; ++t) dz[rt][HT + t] = selu_bwd4(dxr[t], z[rt][HT + t]);
             }
-            if (PMT_BWD_XH4_AT_P3 == 2) {  // behind the phase's last global load, ahead of its cross-lane sums (LDS only)
-                __builtin_amdgcn_sched_barrier(0);
-                load_xh4();
-                __builtin_amdgcn_sched_barrier(0);
-                xh4_requested = true;
-            }
             aux_push_vec_x<HT, EX, AUXCHK>(c, uniform(B.sgu_norm_w_src), dsw, h);
             aux_push_vec_x<HT, EX, AUXCHK>(c, uniform(B.sgu_norm_b_src), dsb, h);
             if constexpr (!LAYERED) push_gate_scalars(d_reg_w, enc_phi(uniform(B.reg_weight_phi)));  // (layered: pushed at the end of the launch that computed them)
@@ -725,9 +692,11 @@ DEV void backward_group(
         trace_ev(c, 22);
         t_ph = prof_now();
         // ---- phase 4: proj1 weight gradient (needs n again), d(n) = W1^T d(zpre), LayerNorm(D) backward ---------------------
+        // xhat_l and its rstd are requested here, where they are used: an earlier request (in phase 1 or 3) holds 32 registers that cost
+        // more than the overlap gives (2.03 - 2.04 ms here; 2.06 - 2.09 requested early)
         {
             f4 n[PMT_RT][NTD];
-            if (!xh4_requested) load_xh4();  // (the generic instances and the later slices of a layered backward: no early request)
+            load_xh4();
             affine_n(n, xh4);
             if constexpr (S::BF16 != 0) wgrad_exchange_bf<2 * HT, NTD, 2, BFB, PMT_BC_OF(S::DIM_D)>(c, M->lin[uniform(B.proj1[0])], M->lin[uniform(B.proj1[1])], dz, n, 1.0f);
             else wgrad_exchange<2 * HT, NTD, 2>(c, M->lin[uniform(B.proj1[0])], M->lin[uniform(B.proj1[1])], dz, n, 1.0f);
@@ -859,11 +828,6 @@ __global__ __launch_bounds__(PMT_THREADS, PMT_BWD_WAVES_PER_SIMD) void pmt_backw
     __shared__ __attribute__((aligned(16))) BwdShared sh;
     const int ngroups = bt.num_groups_dev != nullptr ? uniform(bt.num_groups_dev[0]) : bt.num_groups;  // (device count: graph replay)
     float* priv = PRIV ? partials + (size_t)blockIdx.x * (size_t)emit_len - emit_base : nullptr;  // (the host picks PRIV = (partials != nullptr))
-#if PMT_BWD_PRIO
-    // the second-dispatched half of the workgroup loses every arbitration for its SIMD's issue slots to the older half
-    // (MI355X_MICROARCH.md, two waves per SIMD, item 4): one static priority for it, set once
-    if (threadIdx.x >= PMT_THREADS / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     if (LAYERED && lay.join.on) {
         // joined execution: groups go out by ticket, so the groups that have started always form a prefix and a group never waits
         // for one that nobody will run (pmt_device.hpp: PmtJoin)
@@ -875,12 +839,7 @@ __global__ __launch_bounds__(PMT_THREADS, PMT_BWD_WAVES_PER_SIMD) void pmt_backw
         }
         return;
     }
-#ifdef PMT_X_NOLOOP
-    const int grp = blockIdx.x;
-    if (grp < ngroups) {
-#else
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-#endif
         backward_group<S, LAYERED, PRIV>(M, theta, phi, packed, bt, out, dout, stash, zsum_stash, rstd_stash, gtheta, gphi, gvar, lay, grp, sh, priv);
         lds_barrier();  // the next group reuses the LDS
     }
@@ -930,7 +889,7 @@ static auto priv_kernel() {
 }
 // persistent launch with private partial sums: only the bf16-exchange instances know them
 static bool use_partials(const PmtModel* m, int shape, const float* partials, int rows) {
-    return partials != nullptr && rows > 0 && m->emit_len > 0 && shape >= 2;  // (2, 3, 4, 6: the instances with the bf16 exchange)
+    return partials != nullptr && rows > 0 && m->emit_len > 0 && pmt_shape_has_bf16_exchange(shape);
 }
 static int fold_partials(const PmtModel* model_host, const PmtModel* model_dev, const float* packed, float* partials, int rows,
                          float* grad_theta, float* grad_phi, hipStream_t s) {
@@ -959,10 +918,11 @@ extern "C" int pmt_backward(const PmtModel* model_host, const PmtModel* model_de
     const int grid = part && num_partials < batch->num_groups ? num_partials : batch->num_groups;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // (private rows are a compile-time property of the bf16-exchange instances: use_partials is false for the others)
-    auto kernel = part ? (shape == 4 ? priv_kernel<ShapeP0XD, false>() : shape == 3 ? priv_kernel<ShapeP0XB, false>()
-                          : shape == 2 ? priv_kernel<ShapeP0X, false>() : priv_kernel<ShapeP0T, false>())
-                  : shape == 4 ? pmt_backward_kernel<ShapeP0XD> : shape == 3 ? pmt_backward_kernel<ShapeP0XB> : shape == 2 ? pmt_backward_kernel<ShapeP0X>
-                  : shape == 6 ? pmt_backward_kernel<ShapeP0T> : shape == 1 ? pmt_backward_kernel<ShapeP0> : pmt_backward_kernel<ShapeAny>;
+    auto kernel = part ? (shape == PMT_SHAPE_EXACT_DROPOUT ? priv_kernel<ShapeP0XD, false>() : shape == PMT_SHAPE_EXACT_BF16 ? priv_kernel<ShapeP0XB, false>()
+                          : shape == PMT_SHAPE_EXACT ? priv_kernel<ShapeP0X, false>() : priv_kernel<ShapeP0T, false>())
+                  : shape == PMT_SHAPE_EXACT_DROPOUT ? pmt_backward_kernel<ShapeP0XD> : shape == PMT_SHAPE_EXACT_BF16 ? pmt_backward_kernel<ShapeP0XB>
+                  : shape == PMT_SHAPE_EXACT ? pmt_backward_kernel<ShapeP0X> : shape == PMT_SHAPE_TILES ? pmt_backward_kernel<ShapeP0T>
+                  : shape == PMT_SHAPE_TILES_F32 ? pmt_backward_kernel<ShapeP0> : pmt_backward_kernel<ShapeAny>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(PMT_THREADS), 0, s, model_dev,
                        theta, phi, packed, *batch, *out, *dout, stash, zsum_stash, rstd_stash, grad_theta, grad_phi, grad_variant_embed,
                        PmtBwdLayered{}, part ? grad_partials : nullptr, model_host->emit_base, model_host->emit_len);
@@ -1002,8 +962,8 @@ extern "C" int pmt_backward_layered(const PmtModel* model_host, const PmtModel* 
     const int shape = pmt_shape_for(model_host, batch, true);
     const bool part = use_partials(model_host, shape, grad_partials, num_partials);
     const int grid = part && num_partials < batch->num_groups ? num_partials : batch->num_groups;
-    auto kernel = (shape >= 2 && shape != 6) ? (part ? priv_kernel<ShapeP0X, true>() : pmt_backward_kernel<ShapeP0X, true>)
-                  : (shape == 1 || shape == 6) ? pmt_backward_kernel<ShapeP0, true> : pmt_backward_kernel<ShapeAny, true>;
+    auto kernel = pmt_shape_has_exact_widths(shape) ? (part ? priv_kernel<ShapeP0X, true>() : pmt_backward_kernel<ShapeP0X, true>)
+                  : (shape == PMT_SHAPE_TILES_F32 || shape == PMT_SHAPE_TILES) ? pmt_backward_kernel<ShapeP0, true> : pmt_backward_kernel<ShapeAny, true>;
     int* join_words = reinterpret_cast<int*>(lay.gsum_g + B * nb * PMT_ZW);
     lay.join = PmtJoin{0, join_words + B * nb, join_words, batch->join_fault ? batch->join_fault : join_words + B * nb + 1};
     if (batch->set_groups != nullptr && L > 0) {  // ONE launch: the groups of a split read set join their sums through HBM

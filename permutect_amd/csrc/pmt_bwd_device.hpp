@@ -9,7 +9,7 @@
 // evaluation of the same step.  Two pieces per operand (16 significant bits) and the three first-order MFMAs put the HIP gradients
 // at 7.3e-6 from fp64 -- the size of the reference's own error (7.9e-6 against 7.0e-6 at 4 096 read sets) -- where the six-MFMA
 // form gives 1.1e-6, for 5.8 % of the kernel (scripts/grad_vs_fp64.py, tests/test_scale_gpu.py).  The weight gradients have contracted two-piece operands since round 2.
-// -DPMT_DGRAD_PIECES=3 -DPMT_RECOMPUTE_PIECES=3 restores the six-MFMA form; PMT_TWO_PIECE_MFMAS=5 keeps the second-order terms.
+// -DPMT_DGRAD_PIECES=3 -DPMT_RECOMPUTE_PIECES=3 restores the six-MFMA form (the alt6 library).
 #ifndef PMT_DGRAD_PIECES
 #define PMT_DGRAD_PIECES 2
 #endif
@@ -573,27 +573,12 @@ DEV int stage_rbase(int lane) {  // lane (m = lane & 15, kg = lane >> 4) -> slot
     const int m = lane & 15, kg = lane >> 4;
     return 16 * (16 * kg + (m ^ kg));
 }
-// one operand plane of this wave: v0 / v1 = the plane's registers of tile 0 / tile 1 (zero for padding reads and absent tiles);
-// pj[j] = the wave's stage + (wbase ^ 16 j), off = the plane's byte offset (compile time: it lands in the DS offset fields).
-// Six VALU operations and one ds_write2st64_b32 per pair of values.  The two instructions are spelled out because the
-// optimizer otherwise (a) re-converts v0 alone to get hi << 16 and (b) moves v0, v1 into an aligned register pair to use one
-// v_pk_add_f32 for the two subtractions: nine operations instead of six, a tenth of the backward kernel's VALU work.
-DEV unsigned cvt_pk_bf16(float lo, float hi) {  // round to nearest even
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-DEV float sub_f32(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 DEV char* lds_ptr(unsigned byte_address) {  // an LDS address back as a pointer (address space 3 -> generic)
     return (char*)((__attribute__((address_space(3))) char*)(size_t)byte_address);
 }
-#ifndef PMT_STAGE_BLOCK
-#define PMT_STAGE_BLOCK 1
-#endif
+// Splitting a pair of values into its hi and mid bf16 pieces: six VALU operations per pair.  The instructions are spelled out because the
+// optimizer otherwise (a) re-converts v0 alone to get hi << 16 and (b) moves v0, v1 into an aligned register pair to use one
+// v_pk_add_f32 for the two subtractions: nine operations instead of six, a tenth of the backward kernel's VALU work.
 // (Round 5: forming the residuals of one TILE's two neighbouring values with one v_pk_add_f32 -- ten operations per four values instead of
 //  twelve -- was built and measured EQUAL, 2.16 ms: the staging is not bound by its vector instructions.)
 // Two pairs as ONE instruction block: the same six operations per pair, but interleaved two deep (every result is consumed two
@@ -616,9 +601,14 @@ DEV void split_pairs_block(float a0, float a1, float b0, float b1, unsigned& h0,
         : [h0] "=&v"(h0), [h1] "=&v"(h1), [m0] "=&v"(m0), [m1] "=&v"(m1), [t0] "=&v"(t0), [t1] "=&v"(t1)
         : [a0] "v"(a0), [a1] "v"(a1), [b0] "v"(b0), [b1] "v"(b1));
 }
+// one operand plane of this wave: v0 / v1 = the plane's registers of tile 0 / tile 1 (zero for padding reads and absent tiles);
+// pj[j] = the wave's stage + (wbase ^ 16 j), off = the plane's byte offset (compile time: it lands in the DS offset fields).
 template <int PIECES = 3>
 DEV void stage_pair_bf16(char* const (&pj)[4], int off, f4 v0, f4 v1) {
-    if constexpr (PIECES != 1 && PMT_STAGE_BLOCK) {
+    if constexpr (PIECES == 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<unsigned*>(pj[j] + off) = pack_bf16x2(v0[j], v1[j]);
+    } else {
 #pragma unroll
         for (int j = 0; j < 4; j += 2) {
             unsigned h0, h1, m0, m1;
@@ -627,19 +617,6 @@ DEV void stage_pair_bf16(char* const (&pj)[4], int off, f4 v0, f4 v1) {
             *reinterpret_cast<unsigned*>(pj[j] + off + 1024) = m0;
             *reinterpret_cast<unsigned*>(pj[j + 1] + off) = h1;
             *reinterpret_cast<unsigned*>(pj[j + 1] + off + 1024) = m1;
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        char* p = pj[j] + off;
-        if constexpr (PIECES == 1) {
-            *reinterpret_cast<unsigned*>(p) = pack_bf16x2(v0[j], v1[j]);
-        } else {
-            const unsigned hi = cvt_pk_bf16(v0[j], v1[j]);
-            const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xFFFF0000u);
-            *reinterpret_cast<unsigned*>(p) = hi;
-            *reinterpret_cast<unsigned*>(p + 1024) = cvt_pk_bf16(sub_f32(v0[j], h0), sub_f32(v1[j], h1));
         }
     }
 }

@@ -371,11 +371,7 @@ typedef unsigned c3_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned c3_u2 __attribute__((ext_vector_type(2)));
 // Round 4: the pieces are TWO f16 values per operand with the low one scaled by 2^12 (pmt_device.hpp, linear_acc_f16: fp32-equivalent
 // like three bf16 pieces) -- three MFMAs per product instead of six (conv1: two instead of three), five vector operations per
-// pair of activations instead of nine, 128 bytes of LDS per column instead of 192.  C3_F16 = 0 keeps the bf16 form (A/B runs).
-#ifndef C3_F16
-#define C3_F16 1
-#endif
-#if C3_F16
+// pair of activations instead of nine, 128 bytes of LDS per column instead of 192.
 typedef h8 c3p8;
 #define C3_NP 2
 #define C3_ONE ((unsigned short)0x3C00)  // 1.0 as f16
@@ -393,23 +389,6 @@ DEV void c3p_mma(const c3p8 (&a)[C3_NP], const c3p8 (&b)[C3_NP], f4& acc, f4& lo
     acc = c3p_mfma(a[0], b[0], acc);
 }
 DEV f4 c3p_join(f4 acc, f4 lo) { return lo * (1.0f / 4096.f) + acc; }
-#else
-typedef bf8 c3p8;
-#define C3_NP 3
-#define C3_ONE ((unsigned short)0x3F80)  // 1.0 as bf16
-DEV f4 c3p_mfma(c3p8 a, c3p8 b, f4 c) { return mfma_bf16(a, b, c); }
-DEV void c3p_split(float a, float b, unsigned (&pc)[3]) { split_pair<3>(a, b, pc[0], pc[1], pc[2]); }
-// acc += A B with both operands in three pieces (smallest terms first); lo unused
-DEV void c3p_mma(const c3p8 (&a)[C3_NP], const c3p8 (&b)[C3_NP], f4& acc, f4& lo) {
-    acc = mfma_bf16(a[2], b[0], acc);
-    acc = mfma_bf16(a[0], b[2], acc);
-    acc = mfma_bf16(a[1], b[1], acc);
-    acc = mfma_bf16(a[1], b[0], acc);
-    acc = mfma_bf16(a[0], b[1], acc);
-    acc = mfma_bf16(a[0], b[0], acc);
-}
-DEV f4 c3p_join(f4 acc, f4 lo) { return acc; }
-#endif
 #define C3_COL_BYTES (64 * C3_NP)  // one column of activations in LDS: [piece][32 channels]
 // the A fragment of lane `ln` (row m = ln & 15, k = 8 (ln >> 4) + i) in C3_NP pieces: dst[piece * 64 + ln]
 template <typename F>
@@ -447,7 +426,7 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_forward_bf_kernel(
     const int OHS = S * 10 + C3B_OH_PAD;  // bf16 elements of one variant's one-hot array
     // ---- LDS: [linear weights: L2 x 3 pieces x 1 KiB][biases: 80 floats][staging of conv1 / conv2 weights | the waves' regions]
     unsigned char* base = reinterpret_cast<unsigned char*>(lds);
-    if (C3_F16) fp16_saturate_on();  // (f16 pieces beyond +-65504 saturate, never inf: pmt_device.hpp)
+    fp16_saturate_on();  // (f16 pieces beyond +-65504 saturate, never inf: pmt_device.hpp)
     c3p8* wlb = reinterpret_cast<c3p8*>(base);
     float* bp = reinterpret_cast<float*>(base + L2 * C3_NP * 1024);
     unsigned char* dyn = base + L2 * C3_NP * 1024 + 320;
@@ -551,14 +530,8 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_forward_bf_kernel(
             f4 acc[2] = {b1v[0], b1v[1]};
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {  // (the one-hot is exact in one piece: the weights' pieces against it)
-#if C3_F16
                 const f4 lo = c3p_mfma(w1r[mt][1], b, c3_zero());
                 acc[mt] = c3p_join(c3p_mfma(w1r[mt][0], b, acc[mt]), lo);
-#else
-                acc[mt] = mfma_bf16(w1r[mt][2], b, acc[mt]);
-                acc[mt] = mfma_bf16(w1r[mt][1], b, acc[mt]);
-                acc[mt] = mfma_bf16(w1r[mt][0], b, acc[mt]);
-#endif
             }
             const int q = p >> 1;
             const bool store = in_range && !(p & 1) && q < P1;  // (p + 1 < L1 follows from q < P1 = L1 / 2)

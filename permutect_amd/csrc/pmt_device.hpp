@@ -106,7 +106,7 @@ static_assert(PMT_SH_F <= 16 * PMT_SH_NTF && PMT_SH_F > 16 * (PMT_SH_NTF - 1) &&
               PMT_SH_D <= 16 * PMT_SH_NTD && PMT_SH_D > 16 * (PMT_SH_NTD - 1) && PMT_SH_E <= 16 * PMT_SH_NTE && PMT_SH_E > 16 * (PMT_SH_NTE - 1) &&
               PMT_SH_H >= 1 && PMT_SH_H <= PMT_MAX_HALF_FFN && (PMT_SH_H > 16 * (PMT_HT - 1) || PMT_GENERIC_ONLY_BUILD), "SHAPE: the widths must fill exactly the tile counts given");
 #ifndef PMT_GENERIC_ONLY
-#define PMT_GENERIC_ONLY 0  // 1 (the WIDE build, csrc/Makefile): no exact instances -- every shape below is the generic one, pmt_shape_id is 0
+#define PMT_GENERIC_ONLY 0  // 1 (the WIDE build, csrc/Makefile): no exact instances -- every shape below is the generic one, pmt_shape_id is PMT_SHAPE_ANY
 #endif
 #if PMT_GENERIC_ONLY
 using ShapeP0 = ShapeAny; using ShapeP0X = ShapeAny; using ShapeP0XB = ShapeAny; using ShapeP0XD = ShapeAny; using ShapeP0XH = ShapeAny;
@@ -119,12 +119,12 @@ using ShapeP0XD = Shape<PMT_SH_TILES, true, PMT_SH_DIMS, 3, true>;  // the shape
 // The FORWARD instances of the shape since round 4: the same widths with the products as THREE f16 MFMAs on two-piece
 // splits (XBF = 16 = PMT_F16X2, linear_acc_f16 below; fp32-equivalent like the six bf16 MFMAs).  The backward keeps its bf16
 // pieces (gradients need bf16's exponent range), so ShapeP0X / ShapeP0XD above remain its instances and, for the forward, the
-// round-3 form that PmtModel.force_shape = 5 asks for.
+// round-3 form that PMT_FORCE_FWD_BF16X3 asks for.
 using ShapeP0XH = Shape<PMT_SH_TILES, true, PMT_SH_DIMS, 16>;
 using ShapeP0XHD = Shape<PMT_SH_TILES, true, PMT_SH_DIMS, 16, true>;
 // A model that fills the shape's TILE counts but not its widths (other widths inside the same tiles, or layers of different widths
 // within one MLP -- the reference's test configuration T0: reducer 30 -> 20 -> 20 -> 20) still runs on the 16-bit matrix pipes:
-// the tile-exact instances with the widths read from the descriptor (pmt_shape_id: 6).  Padding positions hold zeros in the
+// the tile-exact instances with the widths read from the descriptor (PMT_SHAPE_TILES).  Padding positions hold zeros in the
 // packed weights and in every activation, so whole tiles are multiplied without guards.
 using ShapeP0T = Shape<PMT_SH_TILES, true, 0, 0, 0, 0, 0, 3>;    // backward (bf16 pieces)
 using ShapeP0TH = Shape<PMT_SH_TILES, true, 0, 0, 0, 0, 0, 16>;  // forward (f16 pieces)
@@ -153,9 +153,6 @@ template <int CTRL>
 DEV int dpp_mov_int(int v, int absent) {  // `absent`: what lanes without a source lane read
     return __builtin_amdgcn_update_dpp(absent, v, CTRL, 0xF, 0xF, false);
 }
-#ifndef PMT_SEG_FMAC
-#define PMT_SEG_FMAC 1
-#endif
 struct SegPlan {
     bool t1, t2, t4, t8;  // lane r - d holds the same set
     bool last;            // the run ends in this lane
@@ -211,7 +208,7 @@ DEV float seg_sum_select(float v, const SegPlan& p) {
 #endif
 template <bool GUARD = true>
 DEV float seg_sum(float v, const SegPlan& p) {  // v must be 0 in lanes without a read
-    if (PMT_SEG_FMAC && (!GUARD || !wave_any(!seg_all_finite(v)))) {
+    if (!GUARD || !wave_any(!seg_all_finite(v))) {
         // v += m_d * (v of lane r - d), d = 1, 2, 4, 8: four fused multiply-adds whose first operand comes through the DPP
         // row shift (lanes without a source lane keep their value; their multiplier is 0 anyway).  Was per step: a move, the
         // DPP move, a select on a scalar-register mask and an add, with two wait states in between -- six issue slots, and
@@ -229,7 +226,7 @@ DEV float seg_sum(float v, const SegPlan& p) {  // v must be 0 in lanes without 
 template <bool GUARD = true>
 DEV f4 seg_sum4(f4 v, const SegPlan& p) {
     const bool finite = !GUARD || (seg_all_finite(v[0]) && seg_all_finite(v[1]) && seg_all_finite(v[2]) && seg_all_finite(v[3]));
-    if (!PMT_SEG_FMAC || (GUARD && wave_any(!finite))) return f4{seg_sum_select(v[0], p), seg_sum_select(v[1], p), seg_sum_select(v[2], p), seg_sum_select(v[3], p)};
+    if (GUARD && wave_any(!finite)) return f4{seg_sum_select(v[0], p), seg_sum_select(v[1], p), seg_sum_select(v[2], p), seg_sum_select(v[3], p)};
     float a = v[0], b = v[1], c = v[2], d = v[3];
 #define PMT_SEG_STEP(M, SH)                                                            \
     "v_fmac_f32_dpp %0, %0, %" #M " row_shr:" #SH " row_mask:0xf bank_mask:0xf\n\t"  \
@@ -269,42 +266,7 @@ DEV float selu1(float x) {
 // 4.5 instead of 7 VALU slots per element; SELU is a third of the non-matrix instructions of the MLP layers.  Same
 // formula and roundings as selu1 except that alpha*scale*(e - 1) is one fused multiply-add (e * c - c).
 typedef float f2 __attribute__((ext_vector_type(2)));
-#ifndef PMT_SELU_MINMAX
-#define PMT_SELU_MINMAX 0
-#endif
-#ifndef PMT_SELU_SCALAR
-#define PMT_SELU_SCALAR 0
-#endif
 DEV f4 selu4(f4 v) {
-    if (PMT_SELU_MINMAX) {
-        // branch-free form: scale * max(x, 0) + min(c e^x - c, 0), c = alpha * scale -- bit for bit the two-branch result (for
-        // x > 0 the second term is 0 and the fma rounds scale * x once; for x <= 0 the first is 0), without the compare /
-        // select pair per element and the wait state between them
-        constexpr float c = PMT_SELU_ALPHA * PMT_SELU_SCALE;
-        f4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float e = __builtin_amdgcn_exp2f(v[i] * 1.4426950408889634f);
-            const float neg = fminf(__builtin_fmaf(e, c, -c), 0.f);
-            r[i] = __builtin_fmaf(PMT_SELU_SCALE, fmaxf(v[i], 0.f), neg);
-        }
-        return r;
-    }
-    if (PMT_SELU_SCALAR) {  // the same arithmetic without the packed fp32 instructions (A/B switch)
-        f4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float t, e, n, p;
-            asm("v_mul_f32 %0, 0x3fb8aa3b, %1" : "=v"(t) : "v"(v[i]));
-            e = __builtin_amdgcn_exp2f(t);
-            constexpr float c = PMT_SELU_ALPHA * PMT_SELU_SCALE;
-            n = __builtin_fmaf(e, c, -c);
-            p = v[i] * PMT_SELU_SCALE;
-            asm volatile("" : "+v"(n), "+v"(p));
-            r[i] = v[i] > 0.f ? p : n;
-        }
-        return r;
-    }
     const f2 lo = f2{v[0], v[1]}, hi = f2{v[2], v[3]};
     const f2 tl = lo * 1.4426950408889634f, th = hi * 1.4426950408889634f;
     const f2 el = f2{__builtin_amdgcn_exp2f(tl[0]), __builtin_amdgcn_exp2f(tl[1])};
@@ -397,31 +359,15 @@ DEV void split_bf16x3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
 }
 // Splitting a pair of values into bf16 pieces: pack (v_cvt_pk_bf16_f32), subtract each half back (shift / mask the half
 // into a float, one v_pk_add_f32 for both), pack the residuals, ...: 9 VALU operations for three pieces, 6 for two.
-// PMT_SPLIT_DOT2 = 1 forms the residuals on the dot-product unit instead (v_dot2c_f32_bf16 with the multiplier pair (-1, 0) or
-// (0, -1): acc - one half, exact, 7 / 4 operations): measured equal in the backward and 6 % SLOWER in the filter forward
-// (0.81 -> 0.86 ms) -- the instruction is not full rate.  Kept as a switch.
+// (Forming the residuals on the dot-product unit, v_dot2c_f32_bf16, takes 7 / 4 operations and was 6 % slower in the filter forward:
+// the instruction is not full rate.)
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 DEV unsigned pack_bf16_pair(float lo, float hi) {  // v_cvt_pk_bf16_f32, round to nearest even
     const bf2 p = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(unsigned, p);
 }
-// (the multiplier pairs travel in registers: as a compile-time constant hipcc 7.2 encodes the pair (-1, 0) = 0x0000BF80 as the
-//  INLINE constant -1.0, which the instruction reads as 0xBF800000 = the pair (0, -1))
-DEV unsigned opaque_bits(unsigned v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-#ifndef PMT_SPLIT_DOT2
-#define PMT_SPLIT_DOT2 0
-#endif
-DEV float minus_lo_half(unsigned pk, float acc) {
-    if (!PMT_SPLIT_DOT2) return acc - __builtin_bit_cast(float, pk << 16);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, pk), __builtin_bit_cast(bf2, opaque_bits(0x0000BF80u)), acc, false);
-}
-DEV float minus_hi_half(unsigned pk, float acc) {
-    if (!PMT_SPLIT_DOT2) return acc - __builtin_bit_cast(float, pk & 0xFFFF0000u);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, pk), __builtin_bit_cast(bf2, opaque_bits(0xBF800000u)), acc, false);
-}
+DEV float minus_lo_half(unsigned pk, float acc) { return acc - __builtin_bit_cast(float, pk << 16); }
+DEV float minus_hi_half(unsigned pk, float acc) { return acc - __builtin_bit_cast(float, pk & 0xFFFF0000u); }
 template <int PIECES>
 DEV void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
     h = pack_bf16_pair(a, b);
@@ -456,19 +402,13 @@ DEV void split_kblock(const f4 (&in)[PMT_RT][NTI], int kb, float in_scale, bf8 (
         if constexpr (PIECES >= 3) bl[rt] = __builtin_bit_cast(bf8, l);
     }
 }
-#ifndef PMT_TWO_PIECE_MFMAS
-#define PMT_TWO_PIECE_MFMAS 3  // MFMAs of a product with two-piece activations: 5 (all but a_hi b_lo) or 3 (first order only)
-#endif
-#ifndef PMT_BF16_K16_TAIL
-#define PMT_BF16_K16_TAIL 0  // 1 (development: reproduces the hazard): the 16-deep MFMA for the half-filled last k block of 3, 5, 7 input tiles
-#endif
 #ifndef PMT_FRAG_AHEAD
 #define PMT_FRAG_AHEAD 0  // the forward (4 waves per SIMD hide the latency; no registers to spare): 1.15 ms -> 1.18 with 1
 #endif
 template <int NTI, int NTO, bool SELU_IN, int PIECES = 3>
 DEV void linear_acc_bf16(f4 (&acc)[PMT_RT][NTO], const f4 (&in)[PMT_RT][NTI], const float* __restrict__ fragb, float in_scale = 1.0f) {
-    // PIECES = pieces of the ACTIVATION: 3 fp32-equivalent (six MFMAs), 2 hi + mid (16 significant bits; five MFMAs against the
-    // three-piece weights), 1 plain bf16.
+    // PIECES = pieces of the ACTIVATION: 3 fp32-equivalent (six MFMAs), 2 hi + mid (16 significant bits; three MFMAs, the first-order
+    // terms only), 1 plain bf16.
     // The weight fragments of step (kb, mt) lie 3 KiB apart in consumption order and come from L2 (a step's weights are
     // ~0.7 MB: far beyond the 32 KiB L1), ~2 x the 12 MFMAs of a step away: they are fetched PMT_FRAG_AHEAD steps ahead, the
     // first ones before the input is split, so that no MFMA group waits for its own loads.
@@ -491,7 +431,7 @@ DEV void linear_acc_bf16(f4 (&acc)[PMT_RT][NTO], const f4 (&in)[PMT_RT][NTI], co
         // accumulator before the longer instruction has written it back -- the hardware interlocks an accumulation chain of ONE opcode
         // only, and hipcc 7.2 puts no wait state between the two (scripts/microbench/mfma_chain_hazard.hip).  Wrong sums whenever
         // the two issue back to back, i.e. depending on what the SIMD's other wave does: the "race" of round 4's split read sets.
-        const bool half_block = (NKB == 1 || PMT_BF16_K16_TAIL) && 2 * kb + 1 >= NTI;
+        constexpr bool half_block = NTI == 1;
 #pragma unroll
         for (int mt = 0; mt < NTO; ++mt) {
             const int step = kb * NTO + mt;
@@ -507,9 +447,9 @@ DEV void linear_acc_bf16(f4 (&acc)[PMT_RT][NTO], const f4 (&in)[PMT_RT][NTI], co
                 const bf8 am = q[step % (AH + 1)][NP > 1 ? 1 : 0], al = q[step % (AH + 1)][NP > 2 ? 2 : 0];
 #pragma unroll
                 for (int rt = 0; rt < PMT_RT; ++rt) {  // smallest terms first
-                    // (two-piece activations drop the a_hi b_lo term, 2^-16 of the product: with PMT_TWO_PIECE_MFMAS = 3 the two
-                    //  other terms of that order, a_lo b_hi and a_mid b_mid, go as well -- three MFMAs, the same error order)
-                    constexpr bool SECOND_ORDER = PIECES == 3 || PMT_TWO_PIECE_MFMAS != 3;
+                    // (two-piece activations drop the a_hi b_lo term, 2^-16 of the product, and with it the two other terms of that
+                    //  order, a_lo b_hi and a_mid b_mid -- three MFMAs, the same error order)
+                    constexpr bool SECOND_ORDER = PIECES == 3;
                     if (half_block) {
                         if constexpr (SECOND_ORDER) acc[rt][mt] = mfma_bf16_k16(al, bh[rt], acc[rt][mt]);
                         if constexpr (PIECES == 3) acc[rt][mt] = mfma_bf16_k16(ah, bl[rt], acc[rt][mt]);
@@ -558,39 +498,23 @@ DEV f4 mfma_f16_k16(h8 a, h8 b, f4 c) {  // the 16-deep variant on elements 0..3
     return __builtin_amdgcn_mfma_f32_16x16x16f16(h4v{a[0], a[1], a[2], a[3]}, h4v{b[0], b[1], b[2], b[3]}, c, 0, 0, 0);
 }
 DEV void fp16_saturate_on() { asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); }  // MODE.FP16_OVFL
-#ifndef PMT_F16_SPLIT_ASM
-#define PMT_F16_SPLIT_ASM 1
-#endif
 DEV void split_pair_f16(float a, float b, unsigned& h, unsigned& l, float k4096) {
-    if (PMT_F16_SPLIT_ASM) {
-        // v_cvt_pk_f16_f32 (round to nearest even); the residuals straight from the packed halves (v_fma_mix_f32 reads an f16
-        // half as an operand: x - h, exact); scaled and rounded by v_fma_mixlo / mixhi_f16 (fp32 product, one rounding)
-        float ra, rb;
-        asm("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
-            "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-            : "=&v"(h), "=&v"(ra), "=&v"(rb) : "v"(a), "v"(b));
-        // (s_nop 1: the packed low pieces go straight into an MFMA as its B operand, and v_fma_mixhi_f16 -- a 16-bit write that keeps the
-        //  other half -- is not home when an MFMA issued right behind it reads the register: wrong low pieces, a 1e-4-relative
-        //  error, in ONE instance (filter forward, 7 + 2 x 2 tiles) until the wait states went in; the compiler does not look for
-        //  hazards behind inline asm.  One wait state was enough on the hardware; two are issued.)
-        asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
-            "v_fma_mixhi_f16 %0, %2, %3, 0\n\t"
-            "s_nop 1"
-            : "=&v"(l) : "v"(ra), "v"(rb), "v"(k4096));
-        return;
-    }
-    const h2v hh = {(_Float16)a, (_Float16)b};
-    const h2v ll = {(_Float16)((a - (float)hh[0]) * 4096.f), (_Float16)((b - (float)hh[1]) * 4096.f)};
-    h = __builtin_bit_cast(unsigned, hh);
-    l = __builtin_bit_cast(unsigned, ll);
+    // v_cvt_pk_f16_f32 (round to nearest even); the residuals straight from the packed halves (v_fma_mix_f32 reads an f16
+    // half as an operand: x - h, exact); scaled and rounded by v_fma_mixlo / mixhi_f16 (fp32 product, one rounding)
+    float ra, rb;
+    asm("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
+        "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+        : "=&v"(h), "=&v"(ra), "=&v"(rb) : "v"(a), "v"(b));
+    // (s_nop 1: the packed low pieces go straight into an MFMA as its B operand, and v_fma_mixhi_f16 -- a 16-bit write that keeps the
+    //  other half -- is not home when an MFMA issued right behind it reads the register: wrong low pieces, a 1e-4-relative
+    //  error, in ONE instance (filter forward, 7 + 2 x 2 tiles) until the wait states went in; the compiler does not look for
+    //  hazards behind inline asm.  One wait state was enough on the hardware; two are issued.)
+    asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
+        "v_fma_mixhi_f16 %0, %2, %3, 0\n\t"
+        "s_nop 1"
+        : "=&v"(l) : "v"(ra), "v"(rb), "v"(k4096));
 }
-#ifndef PMT_F16_K16_TAIL
-#define PMT_F16_K16_TAIL 0  // 1: the 16-deep MFMA for the half-filled last k block of 3, 5, 7 input tiles too (see linear_acc_f16)
-#endif
-#ifndef PMT_F16_AHEAD
-#define PMT_F16_AHEAD 0  // weight fragments of the next (out tile, k block) step requested one step ahead (8 more registers)
-#endif
 // X1: the input is exact in ONE f16 piece (packed read rows: bits and k / 32 quantiles; float16 read rows): no low piece is made and
 // the wh * xl' product is skipped -- two MFMAs per product.
 template <int NTI, int NTO, bool SELU_IN, bool X1 = false>
@@ -632,9 +556,6 @@ DEV void linear_acc_f16(f4 (&acc)[PMT_RT][NTO], const f4 (&in)[PMT_RT][NTI], con
             xh[kb][rt] = __builtin_bit_cast(h8, u4v{hh[0], hh[1], hh[2], hh[3]});
             xl[kb][rt] = __builtin_bit_cast(h8, u4v{ll[0], ll[1], ll[2], ll[3]});
         }
-    constexpr int NSTEP = NTO * NKB;
-    h8 qh[2], ql[2];
-    if (PMT_F16_AHEAD) { qh[0] = fp[0]; ql[0] = fp[64]; }
 #pragma unroll
     for (int mt = 0; mt < NTO; ++mt) {
         f4 lo[PMT_RT];
@@ -643,17 +564,12 @@ DEV void linear_acc_f16(f4 (&acc)[PMT_RT][NTO], const f4 (&in)[PMT_RT][NTI], con
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
             const int step = mt * NKB + kb;
-            h8 ah, al;
-            if (PMT_F16_AHEAD) {
-                ah = qh[step & 1]; al = ql[step & 1];
-                if (step + 1 < NSTEP) { qh[(step + 1) & 1] = fp[128 * (step + 1)]; ql[(step + 1) & 1] = fp[128 * (step + 1) + 64]; }
-            } else {
-                ah = fp[128 * step]; al = fp[128 * step + 64];
-            }
+            // (requested where they are used: fetched one step ahead they cost 8 more registers, which the forward does not have)
+            const h8 ah = fp[128 * step], al = fp[128 * step + 64];
             // a k block with one tile only (NTI == 1): the 16-deep MFMA on the lower halves.  The half-filled LAST block of 3, 5 or 7 input
             // tiles (the wide build's shapes) takes the 32-deep one on its zero-padded operands instead: a 16-deep f16 MFMA chained
             // behind 32-deep ones on the same accumulator gave wrong sums (measured, scripts/wide_debug.py)
-            const bool half_block = (NKB == 1 || PMT_F16_K16_TAIL) && 2 * kb + 1 >= NTI;
+            constexpr bool half_block = NTI == 1;
 #pragma unroll
             for (int rt = 0; rt < PMT_RT; ++rt) {
                 if (half_block) {
@@ -745,33 +661,18 @@ DEV float* grad_ptr(int src, float* gtheta, float* gphi) { return src >= 0 ? gth
 
 // ---- stash layout (floats per 16-read tile) ---------------------------------------------------------------------
 // slots: [read-MLP op boundaries 1..n-1][x_0 .. x_L][reducer op boundaries 1..n-1], each slot NT*256 floats
-#ifndef PMT_STASH_Z
-#define PMT_STASH_Z 1  // 1: the blocks' z in the stash; 0: the backward recomputes it.  Measured again in round 3, when the training forward had
-                       // turned out to be bound by its stash WRITES (3.0 GB per 65 536-set launch at ~3.5 TB/s) and the layers'
-                       // recomputation had dropped to three MFMAs per product: without z (22 % of the stash) the forward gains 40 us,
-                       // but the gate multiplies by z, and recomputed on two bf16 pieces it puts the gradients 5e-5 from fp64 (7e-6
-                       // with z stashed); recomputed on three pieces the backward pays 70 us.  z stays in the stash.
-#endif
 // stash slots per tile: the inputs of the read MLP's ops 1.., xhat_0 .. xhat_{L-1} and x_L, the inputs of the reducer's ops 1..,
-// then every block's z (after SELU; half a slot used)
+// then every block's z (after SELU; half a slot used).  z stays in the stash: without it (22 % of the stash) the training forward, which
+// is bound by its stash writes, gains 40 us, but the gate multiplies by z, and recomputed on two bf16 pieces it puts the gradients 5e-5
+// from fp64 (7e-6 with z stashed); recomputed on three pieces the backward pays 70 us.
 DEV int stash_num_slots(const PmtModel* M) { return (M->read_mlp.n_ops - 1) + (M->num_blocks + 1) + (M->reducer.n_ops - 1) + M->num_blocks; }
 #define PMT_SLOT_FLOATS (PMT_NT * 256)
 
-#ifndef PMT_STASH_NT
-#define PMT_STASH_NT 1
-#endif
-#ifndef PMT_STASH_EXPERIMENT
-#define PMT_STASH_EXPERIMENT 0
-#endif
 template <int NT>
 DEV void stash_store(float* __restrict__ base, const f4 (&v)[NT]) {
-    if (PMT_STASH_EXPERIMENT == 1) return;  // development knock-out (timing only): no stash stores at all
     f4* p = reinterpret_cast<f4*>(base) + (pmt_tid() & 63);
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        if (PMT_STASH_NT) __builtin_nontemporal_store(v[t], p + t * 64);  // written once, read by the backward long after
-        else p[t * 64] = v[t];
-    }
+    for (int t = 0; t < NT; ++t) __builtin_nontemporal_store(v[t], p + t * 64);  // written once, read by the backward long after
 }
 template <int NT>
 DEV void stash_load(const float* __restrict__ base, f4 (&v)[NT]) {
@@ -991,14 +892,22 @@ DEV void drop_apply(const PmtDrop& d, int lin, f4 (&y)[PMT_RT][NT], int g) {
 }
 
 extern "C" int pmt_stash_slots(const PmtModel* m);  // host helper (pmt_host.hip)
-extern "C" int pmt_shape_id(const PmtModel* m);     // host: 2 = ShapeP0X (exact widths), 6 = ShapeP0T (exact tiles, 16-bit pipes), 1 = ShapeP0 (exact tiles, fp32 MFMAs: asked for only), 0 = ShapeAny
-// A batch that brings a dropout seed to a model with dropout_p > 0 runs an instance that carries the masks: 4 = ShapeP0XD (the
-// production shape, one-launch path only), else 0 = the generic instance.
+extern "C" int pmt_shape_id(const PmtModel* m);     // host: the instance a model runs (permutect_amd.h: PMT_SHAPE_*)
+// A batch that brings a dropout seed to a model with dropout_p > 0 runs an instance that carries the masks: ShapeP0XD (the
+// production shape, one-launch path only), else the generic instance.
 static inline int pmt_shape_for(const PmtModel* m, const PmtBatch* b, bool layered = false) {
     int shape = pmt_shape_id(m);
-    if (shape == 6 && layered) shape = 1;  // (split read sets of a tile-exact model: the fp32 tile-exact instances)
+    if (shape == PMT_SHAPE_TILES && layered) shape = PMT_SHAPE_TILES_F32;  // (split read sets of a tile-exact model: the fp32 tile-exact instances)
     if (!(m->dropout_p > 0.f && b->dropout_seed != 0)) return shape;
-    return (shape == 2 && !layered) ? 4 : 0;
+    return (shape == PMT_SHAPE_EXACT && !layered) ? PMT_SHAPE_EXACT_DROPOUT : PMT_SHAPE_ANY;
+}
+// this instance has the bf16 weight-gradient exchange (every instance on the 16-bit matrix pipes)
+static inline bool pmt_shape_has_bf16_exchange(int shape) {
+    return shape == PMT_SHAPE_EXACT || shape == PMT_SHAPE_EXACT_BF16 || shape == PMT_SHAPE_EXACT_DROPOUT || shape == PMT_SHAPE_TILES;
+}
+// this instance has the build's widths compiled in (split read sets run ShapeP0X / ShapeP0XH for all of them)
+static inline bool pmt_shape_has_exact_widths(int shape) {
+    return shape == PMT_SHAPE_EXACT || shape == PMT_SHAPE_EXACT_BF16 || shape == PMT_SHAPE_EXACT_DROPOUT;
 }
 
 DEV int frag_floats_dev(const PmtLinear& L) {

@@ -7,12 +7,6 @@
 #include "pmt_device.hpp"
 #include "pmt_mlp_device.hpp"
 
-#ifndef PMT_LAYERED_WIDE
-#define PMT_LAYERED_WIDE 0  // 1: the instances for split read sets at 256 registers / two waves per SIMD (A/B switch)
-#endif
-#ifndef PMT_F16_X1
-#define PMT_F16_X1 1  // the first read-MLP linear on one-piece inputs (0: two pieces like every other layer; A/B switch)
-#endif
 struct FwdShared {  // (the float tables first: their rows are read and cleared 16 bytes at a time)
     float zsum[3][PMT_GROUP_MAX_SETS][2][16 * PMT_HT];
     float fsum[PMT_GROUP_MAX_SETS][2][PMT_MAX_WIDTH];
@@ -38,14 +32,11 @@ DEV float read_feature(const unsigned char* __restrict__ row, int fmt, int f, in
 }
 
 // an activation array about to become a pair of f16 operand pieces: any value beyond their range goes into the caller's fault word
-// (v_max3 over the registers, one compare, one ballot; NaN compares false: a non-finite stream shows in the outputs themselves)
-#ifndef PMT_F16_RANGE_CHECK
-#define PMT_F16_RANGE_CHECK 6  // bits: 2 the residual stream at the reducer, 4 the reducer's output (both free).  (Read rows need no check:
-                               // the f16 instances run packed rows only, whose values are below 8 -- wide_range_operands.)
-#endif
-template <int NT, int WHICH>
+// (v_max3 over the registers, one compare, one ballot; NaN compares false: a non-finite stream shows in the outputs themselves).  Checked:
+// the residual stream at the reducer and the reducer's output (both free).  Read rows need no check: the f16 instances run packed rows
+// only, whose values are below 8 -- wide_range_operands.
+template <int NT>
 DEV void f16_range_check(const f4 (&v)[PMT_RT][NT], int* __restrict__ fault) {
-    if (!(PMT_F16_RANGE_CHECK & WHICH)) return;
     float m = 0.f;
 #pragma unroll
     for (int rt = 0; rt < PMT_RT; ++rt)
@@ -99,7 +90,7 @@ struct FwdTrace {
 };
 
 template <bool TRAIN, typename S, bool LAYERED = false>
-__global__ __launch_bounds__(PMT_THREADS, (S::EXACT && PMT_NT <= 4 && !(LAYERED && PMT_LAYERED_WIDE)) ? 4 : 2) void pmt_forward_kernel(const PmtModel* __restrict__ M,
+__global__ __launch_bounds__(PMT_THREADS, (S::EXACT && PMT_NT <= 4) ? 4 : 2) void pmt_forward_kernel(const PmtModel* __restrict__ M,
                                                                       const float* __restrict__ theta,
                                                                       const float* __restrict__ phi,
                                                                       const float* __restrict__ packed, PmtBatch bt,
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(PMT_THREADS, (S::EXACT && PMT_NT <= 4 && !(LAYERED 
                 for (int rt = 0; rt < PMT_RT; ++rt) drop.row[rt] = tm[rt].row;
             }
             // packed rows (bits, k / 32 quantiles) and float16 rows are exact in ONE f16 piece: no low piece, two MFMAs per product
-            if (PMT_F16_X1 && S::BF16 == PMT_F16X2 && fmt != PMT_READS_F32)
+            if (S::BF16 == PMT_F16X2 && fmt != PMT_READS_F32)
                 run_linear_op<NTF, NTR, true, S::DIM_F, S::DIM_R, S::BF16, S::DROP, true>(M, M->read_mlp.ops[0], xr, xf, g, packed, &drop);
             else
                 run_linear_op<NTF, NTR, true, S::DIM_F, S::DIM_R, S::BF16, S::DROP>(M, M->read_mlp.ops[0], xr, xf, g, packed, &drop);
@@ -313,7 +304,7 @@ __global__ __launch_bounds__(PMT_THREADS, (S::EXACT && PMT_NT <= 4 && !(LAYERED 
                 z[rt][t] = selu4(z[rt][t]);
                 zin[t] = selu4(z[rt][HT + t]);
             }
-            if (TRAIN && EX && PMT_STASH_Z && (mask_all & (1u << rt))) {  // the (exact-width) backward starts the block from these instead of recomputing them
+            if (TRAIN && EX && (mask_all & (1u << rt))) {  // the (exact-width) backward starts the block from these instead of recomputing them
                 f4 zs[2 * HT];
 #pragma unroll
                 for (int t = 0; t < HT; ++t) { zs[t] = z[rt][t]; zs[HT + t] = zin[t]; }
@@ -428,7 +419,7 @@ __global__ __launch_bounds__(PMT_THREADS, (S::EXACT && PMT_NT <= 4 && !(LAYERED 
     // SELU of one, and the read MLP's inputs are bytes; the ONE place an unnormalised activation of any size becomes a matrix
     // operand is here, where the residual stream x_L enters the reducer (and, below, where the reducer's output enters the
     // rotation).  A value beyond the range is reported in the caller's fault word (bit 1), never silently clipped.
-    if constexpr (S::BF16 == PMT_F16X2) f16_range_check<NTD, 2>(x, bt.join_fault);
+    if constexpr (S::BF16 == PMT_F16X2) f16_range_check<NTD>(x, bt.join_fault);
 
     tr.ev(19);
     // ---- reducer MLP, then translation + rotation ----------------------------------------------------------------
@@ -471,7 +462,7 @@ __global__ __launch_bounds__(PMT_THREADS, (S::EXACT && PMT_NT <= 4 && !(LAYERED 
                 a[rt][t] = f4{0.f, 0.f, 0.f, 0.f};
             }
         }
-        if constexpr (S::BF16 == PMT_F16X2) f16_range_check<NTE, 4>(e, bt.join_fault);
+        if constexpr (S::BF16 == PMT_F16X2) f16_range_check<NTE>(e, bt.join_fault);
         if constexpr (S::BF16) linear_acc_mx<NTE, NTE, false, S::BF16>(a, e, packed, R);
         else linear_acc<NTE, NTE, false, EX, S::DIM_E>(a, e, stR, E, E);
     }
@@ -646,11 +637,11 @@ extern "C" int pmt_forward_launch_train_p0x(int groups, void* stream, const PmtM
                                             const float* packed, const PmtBatch* batch, const PmtOutputs* out, float* stash,
                                             float* zsum_stash, float* rstd_stash, const PmtLayeredArgs* lay, int bf16x3) {
 #if PMT_GENERIC_ONLY
-    return PMT_E_UNSUPPORTED;  // (never asked for: pmt_shape_id is 0 in this build)
+    return PMT_E_UNSUPPORTED;  // (never asked for: pmt_shape_id is PMT_SHAPE_ANY in this build)
 #else
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const PmtLayeredArgs none{};
-    // bf16x3 (PmtModel.force_shape = 5): the round-3 instances, six bf16 MFMAs per product; otherwise three f16 MFMAs
+    // bf16x3 (PMT_FORCE_FWD_BF16X3): the round-3 instances, six bf16 MFMAs per product; otherwise three f16 MFMAs
 #define PMT_LAUNCH_FWD(TRAIN, SHAPE, LAYERED, LAY) \
     hipLaunchKernelGGL((pmt_forward_kernel<TRAIN, SHAPE, LAYERED>), dim3(groups), dim3(PMT_THREADS), 0, s, model_dev, theta, phi, packed, \
                        *batch, *out, stash, zsum_stash, rstd_stash, LAY)
@@ -679,7 +670,7 @@ extern "C" int pmt_forward_launch_train_p0x(int groups, void* stream, const PmtM
 // that share its row of 16 lanes -- so they take the instances whose operands carry fp32's range and whose scans are
 // guarded: three bf16 pieces (round 3's form, 1.3 x the time) or, for a tile-exact model, fp32 MFMAs.  The reference's semantics then
 // hold: a non-finite read makes ITS variant's outputs non-finite and no other's (sets/ragged_sets.py:144-158).
-static bool wide_range_operands(const PmtModel* m, const PmtBatch* b) { return m->force_shape == 5 || b->read_format != PMT_READS_PACKED_U8; }
+static bool wide_range_operands(const PmtModel* m, const PmtBatch* b) { return m->force_shape == PMT_FORCE_FWD_BF16X3 || b->read_format != PMT_READS_PACKED_U8; }
 
 // per-set outputs from the global sums of a layered forward (same arithmetic as the finalisation above)
 __global__ __launch_bounds__(256) void pmt_finalize_kernel(const PmtModel* __restrict__ M, const float* __restrict__ phi, PmtBatch bt,
@@ -730,7 +721,7 @@ extern "C" int pmt_forward_layered(const PmtModel* model_host, const PmtModel* m
         return PMT_E_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int shape = pmt_shape_for(model_host, batch, true);
-    const bool p0 = shape == 1;
+    const bool p0 = shape == PMT_SHAPE_TILES_F32;
     const int L = model_host->num_blocks;
     const size_t nb = (size_t)(L > 0 ? L : 1), B = (size_t)batch->num_variants;
     PmtLayeredArgs lay;
@@ -759,7 +750,7 @@ extern "C" int pmt_forward_layered(const PmtModel* model_host, const PmtModel* m
     }
     for (int slice = 0; slice <= (lay.join.on ? 0 : L); ++slice) {
         lay.slice = slice;
-        if (shape >= 2) {  // the layered instances of the production shape: pmt_forward_train.hip  (layered: no plain-bf16 instance)
+        if (pmt_shape_has_exact_widths(shape)) {  // the layered instances of the production shape: pmt_forward_train.hip  (layered: no plain-bf16 instance)
             const int rct = pmt_forward_launch_train_p0x(batch->num_groups, stream, model_dev, theta, phi, packed, batch, out, stash, zsum_stash,
                                                          rstd_stash, &lay, wide_range_operands(model_host, batch));
             if (rct != PMT_OK) return rct;
@@ -786,9 +777,9 @@ extern "C" int pmt_forward(const PmtModel* model_host, const PmtModel* model_dev
         return PMT_E_INVALID;
     if (batch->group_span) return PMT_E_UNSUPPORTED;  // split read sets: pmt_forward_layered
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int shape = pmt_shape_for(model_host, batch);  // pmt_device.hpp: 2 ShapeP0X, 1 ShapeP0, 0 ShapeAny, 4 ShapeP0XD (dropout step)
-    if (shape == 4 && !stash) shape = 0;            // (train mode without a backward to follow: the generic instance)
-    const bool p0 = shape == 1;
+    int shape = pmt_shape_for(model_host, batch);
+    if (shape == PMT_SHAPE_EXACT_DROPOUT && !stash) shape = PMT_SHAPE_ANY;  // (train mode without a backward to follow: the generic instance)
+    const bool p0 = shape == PMT_SHAPE_TILES_F32;
     float* zsum_stash = nullptr;
     float* rstd_stash = nullptr;
     if (stash) {
@@ -800,14 +791,14 @@ extern "C" int pmt_forward(const PmtModel* model_host, const PmtModel* model_dev
     auto kernel = stash ? (p0 ? pmt_forward_kernel<true, ShapeP0> : pmt_forward_kernel<true, ShapeAny>)
                         : (p0 ? pmt_forward_kernel<false, ShapeP0> : pmt_forward_kernel<false, ShapeAny>);
     const bool wide_range = wide_range_operands(model_host, batch);
-    if ((shape == 2 || shape == 4) && stash)  // its own translation unit (pmt_forward_train.hip); 4: with the step's dropout masks
+    if ((shape == PMT_SHAPE_EXACT || shape == PMT_SHAPE_EXACT_DROPOUT) && stash)  // its own translation unit (pmt_forward_train.hip)
         return pmt_forward_launch_train_p0x(batch->num_groups, stream, model_dev, theta, phi, packed, batch, out, stash, zsum_stash, rstd_stash, nullptr,
                                             wide_range);
-    if (shape == 2) kernel = wide_range ? pmt_forward_kernel<false, ShapeP0X> : pmt_forward_kernel<false, ShapeP0XH>;
+    if (shape == PMT_SHAPE_EXACT) kernel = wide_range ? pmt_forward_kernel<false, ShapeP0X> : pmt_forward_kernel<false, ShapeP0XH>;
     // the shape's tiles, widths at run time: f16 pieces -- or, for read rows that can hold anything, the fp32 tile-exact instance (`kernel` above)
-    if (shape == 6 && !wide_range) kernel = stash ? pmt_forward_kernel<true, ShapeP0TH> : pmt_forward_kernel<false, ShapeP0TH>;
-    if (shape == 6 && wide_range) kernel = stash ? pmt_forward_kernel<true, ShapeP0> : pmt_forward_kernel<false, ShapeP0>;
-    if (shape == 3) kernel = stash ? pmt_forward_kernel<true, ShapeP0XB> : pmt_forward_kernel<false, ShapeP0XB>;  // plain bf16 products
+    if (shape == PMT_SHAPE_TILES && !wide_range) kernel = stash ? pmt_forward_kernel<true, ShapeP0TH> : pmt_forward_kernel<false, ShapeP0TH>;
+    if (shape == PMT_SHAPE_TILES && wide_range) kernel = stash ? pmt_forward_kernel<true, ShapeP0> : pmt_forward_kernel<false, ShapeP0>;
+    if (shape == PMT_SHAPE_EXACT_BF16) kernel = stash ? pmt_forward_kernel<true, ShapeP0XB> : pmt_forward_kernel<false, ShapeP0XB>;  // plain bf16 products
     hipLaunchKernelGGL(kernel, dim3(batch->num_groups), dim3(PMT_THREADS), 0, s, model_dev, theta, phi, packed, *batch, *out,
                        stash, zsum_stash, rstd_stash, PmtLayeredArgs{});
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;

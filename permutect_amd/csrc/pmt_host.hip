@@ -51,14 +51,14 @@ extern "C" int pmt_struct_bytes(int which) {
 extern "C" int pmt_stash_slots(const PmtModel* m) { return (m->read_mlp.n_ops - 1) + (m->num_blocks + 1) + (m->reducer.n_ops - 1) + m->num_blocks; }
 
 // Which register-array shape the read-set kernels run with (pmt_device.hpp: Shape; the tile counts and widths of the exact
-// instances are the BUILD's shape, PMT_SH_*: the production hyperparameters by default).
-//   0 = ShapeAny: any supported model (fp32 MFMAs, every tile guarded);
-//   1 = ShapeP0: every layer fills the shape's tile arrays exactly -- read features and the first read linear NTF -> NTR tiles, the
-//       rest of the read MLP NTR wide, d_model and the reducer NTD wide up to a last LINEAR NTD -> NTE, feature_dim NTE -- fp32
-//       MFMAs, widths at run time (PmtModel.force_shape = 1 only);
-//   6 = ShapeP0T / ShapeP0TH: the same tile-exact models on the 16-bit matrix pipes, widths at run time;
-//   2 = ShapeP0X / ShapeP0XH: additionally every width equals the build's (compiled in); 3 = the same with plain bf16 products.
-// PmtModel.force_shape = 2 / 1 forces the generic / the fp32 tile-exact instance (the parity tests cover all).
+// instances are the BUILD's shape, PMT_SH_*: the production hyperparameters by default).  The ids: permutect_amd.h, PMT_SHAPE_*.
+//   ANY = ShapeAny: any supported model;
+//   TILES_F32 = ShapeP0: every layer fills the shape's tile arrays exactly -- read features and the first read linear NTF -> NTR tiles,
+//       the rest of the read MLP NTR wide, d_model and the reducer NTD wide up to a last LINEAR NTD -> NTE, feature_dim NTE -- fp32
+//       MFMAs, widths at run time (PMT_FORCE_TILES_F32 only);
+//   TILES = ShapeP0T / ShapeP0TH: the same tile-exact models on the 16-bit matrix pipes, widths at run time;
+//   EXACT = ShapeP0X / ShapeP0XH: additionally every width equals the build's (compiled in); EXACT_BF16 = the same with plain bf16 products.
+// PMT_FORCE_ANY / PMT_FORCE_TILES_F32 force the generic / the fp32 tile-exact instance (the parity tests cover all).
 extern "C" int pmt_shape_info(int32_t* nine) {  // the build's shape: tile counts NTF, NTR, NTD, NTE, then widths F, R, D, H, E
     const int32_t v[9] = {PMT_SH_NTF, PMT_SH_NTR, PMT_SH_NTD, PMT_SH_NTE, PMT_SH_F, PMT_SH_R, PMT_SH_D, PMT_SH_H, PMT_SH_E};
     if (nine) memcpy(nine, v, sizeof(v));
@@ -94,27 +94,27 @@ extern "C" int pmt_limits(int32_t* four) {  // the build's compile-time limits: 
     return PMT_OK;
 }
 extern "C" int pmt_shape_id(const PmtModel* m) {
-    if (m->force_shape == 2 || PMT_GENERIC_ONLY) return 0;  // (5 = auto for every kernel but the forward, whose launchers read it themselves)
+    if (m->force_shape == PMT_FORCE_ANY || PMT_GENERIC_ONLY) return PMT_SHAPE_ANY;  // (PMT_FORCE_FWD_BF16X3 = auto for every kernel but the forward, whose launchers read it themselves)
     const PmtMlp* rm = &m->read_mlp;
     const PmtMlp* red = &m->reducer;
-    if (rm->n_ops < 1 || red->n_ops < 1 || m->num_blocks < 0) return 0;
+    if (rm->n_ops < 1 || red->n_ops < 1 || m->num_blocks < 0) return PMT_SHAPE_ANY;
     const PmtOp* first = &rm->ops[0];
     const PmtOp* last = &red->ops[red->n_ops - 1];
-    if (first->kind != PMT_OP_LINEAR || last->kind != PMT_OP_LINEAR) return 0;
+    if (first->kind != PMT_OP_LINEAR || last->kind != PMT_OP_LINEAR) return PMT_SHAPE_ANY;
     const PmtLinear* Lf = &m->lin[first->lin[0]];
     const PmtLinear* Ll = &m->lin[last->lin[0]];
     const bool ok = tiles_of(m->num_read_features) == PMT_SH_NTF && tiles_of(Lf->in_dim) == PMT_SH_NTF && tiles_of(Lf->out_dim) == PMT_SH_NTR &&
                     mlp_ops_have_tiles(m, rm, 1, rm->n_ops, PMT_SH_NTR) && tiles_of(m->read_embed_dim) == PMT_SH_NTR &&
                     tiles_of(m->d_model) == PMT_SH_NTD && m->d_ffn >= 2 && mlp_ops_have_tiles(m, red, 0, red->n_ops - 1, PMT_SH_NTD) &&
                     tiles_of(Ll->in_dim) == PMT_SH_NTD && tiles_of(Ll->out_dim) == PMT_SH_NTE && tiles_of(m->feature_dim) == PMT_SH_NTE;
-    if (!ok) return 0;
-    if (m->force_shape == 1) return 1;
+    if (!ok) return PMT_SHAPE_ANY;
+    if (m->force_shape == PMT_FORCE_TILES_F32) return PMT_SHAPE_TILES_F32;
     const bool exact = m->num_read_features == PMT_SH_F && Lf->in_dim == PMT_SH_F && Lf->out_dim == PMT_SH_R &&
                        mlp_ops_have_width(m, rm, 1, rm->n_ops, PMT_SH_R) && m->read_embed_dim == PMT_SH_R && m->d_model == PMT_SH_D &&
                        m->d_ffn == 2 * PMT_SH_H && mlp_ops_have_width(m, red, 0, red->n_ops - 1, PMT_SH_D) && Ll->in_dim == PMT_SH_D &&
                        Ll->out_dim == PMT_SH_E && m->feature_dim == PMT_SH_E;
-    if (!exact) return 6;  // the shape's tiles, other widths: the 16-bit pipes with the widths read at run time
-    return m->force_shape == 3 ? 3 : 2;  // 3: the exact widths with plain bf16 products (asked for explicitly only)
+    if (!exact) return PMT_SHAPE_TILES;  // the shape's tiles, other widths: the 16-bit pipes with the widths read at run time
+    return m->force_shape == PMT_FORCE_EXACT_BF16 ? PMT_SHAPE_EXACT_BF16 : PMT_SHAPE_EXACT;  // (plain bf16 products: asked for explicitly only)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -651,7 +651,7 @@ DEV int split_row(int v, int h) {
 // one job per workgroup: (lin, 0) forward frags, (lin, 1) transposed frags, (lin, 2) bias, (lin, 3 / 4) the same two matrices
 // as bf16 pieces, (lin, 5) the weight-gradient emit table, (lin, 6) the forward matrix as two f16 pieces, then per-block vectors
 #define PMT_PACK_KINDS 7
-// bias_cols: the model runs the exact-width instances of the read-set backward (pmt_shape_id 2 / 3), whose weight-gradient exchange sums
+// bias_cols: the model runs the exact-width instances of the read-set backward (PMT_SHAPE_EXACT / _EXACT_BF16), whose weight-gradient exchange sums
 // a bias gradient in the padding column in_dim of dW (pmt_bwd_device.hpp: PMT_BC_OF)
 __global__ void pmt_pack_kernel(const PmtModel* __restrict__ M, const float* __restrict__ theta,
                                 const float* __restrict__ phi, float* __restrict__ packed, int bias_cols) {
@@ -819,7 +819,7 @@ extern "C" int pmt_pack_params(const PmtModel* model_host, const PmtModel* model
     const int jobs = model_host->n_linear * PMT_PACK_KINDS + model_host->num_blocks * 5 + 1;
     const int shape = pmt_shape_id(model_host);
     hipLaunchKernelGGL(pmt_pack_kernel, dim3(jobs), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), model_dev, theta,
-                       phi, packed, (shape == 2 || shape == 3) ? 1 : 0);
+                       phi, packed, (shape == PMT_SHAPE_EXACT || shape == PMT_SHAPE_EXACT_BF16) ? 1 : 0);
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
 }
 

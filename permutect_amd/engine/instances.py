@@ -216,7 +216,7 @@ def library_for(desc: L.PmtModel, log=print) -> C.CDLL:
                       f"{L.limits_of(default)['max_half_ffn']}) has no exact instances for its shape: it runs the WIDE build of the library, GENERIC "
                       "instances (fp32 MFMAs, 8-tile register arrays with spills: several times slower per read than exact-width kernels)")
         return wide_library(log, half32=ht > 1)
-    if desc.force_shape == 2 or (not wide and default.pmt_shape_id(C.byref(desc)) != 0):
+    if desc.force_shape == L.FORCE_ANY or (not wide and default.pmt_shape_id(C.byref(desc)) != L.SHAPE_ANY):
         return generic()
     shape = exact_shape_of(desc)
     if shape is None:
@@ -232,7 +232,7 @@ def library_for(desc: L.PmtModel, log=print) -> C.CDLL:
         candidates += ([exact] if os.path.exists(exact) else []) + sorted(glob.glob(os.path.join(d, f"libpermutect_amd_{_tag(shape[:4])}_*.so")))
     def fits(lib):
         lim = L.limits_of(lib)
-        return lim["max_width"] >= widest and lim["max_half_ffn"] // 16 == ht and lib.pmt_shape_id(C.byref(desc)) != 0
+        return lim["max_width"] >= widest and lim["max_half_ffn"] // 16 == ht and lib.pmt_shape_id(C.byref(desc)) != L.SHAPE_ANY
     stale = []
     for path in dict.fromkeys(candidates):
         if not is_current(path):

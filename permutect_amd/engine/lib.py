@@ -31,6 +31,9 @@ POSTERIOR_RAW, POSTERIOR_PARTIAL = 80, 128  # PMT_POSTERIOR_RAW, PMT_POSTERIOR_P
 
 STEP_ON_DEVICE, STEP_SLOT = -1, 1000
 E_INVALID, E_UNSUPPORTED, E_CAPACITY, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4, -5
+# what pmt_shape_id returns (PMT_SHAPE_*) and what PmtModel.force_shape takes (PMT_FORCE_*)
+SHAPE_ANY, SHAPE_TILES_F32, SHAPE_EXACT, SHAPE_EXACT_BF16, SHAPE_EXACT_DROPOUT, SHAPE_TILES = 0, 1, 2, 3, 4, 6
+FORCE_AUTO, FORCE_TILES_F32, FORCE_ANY, FORCE_EXACT_BF16, FORCE_FWD_BF16X3 = 0, 1, 2, 3, 5
 _ERR = {-1: "invalid argument/descriptor", -2: "configuration not supported by the gfx950 kernels",
         -3: "a read set exceeds the register-resident group capacity", -4: "HIP launch failure",
         -5: "workspace too small"}

@@ -592,3 +592,26 @@ def test_the_row_kernel_tables_reference_side_works_on_every_row(monkeypatch):
         model, _ = T.make_model(T.INFO, in_dim, layers, CPU)
         with pytest.raises(L.PmtError, match=message):
             EnginePlan(model, ParamSpace(model, CPU), CPU)
+
+
+def test_every_build_switch_of_the_kernel_sources_is_in_designs_table():
+    """The kernel sources once carried some forty compile-time switches, half of them rejected experiments nobody took out.  A switch now
+    has to be written down to exist: every macro that permutect_amd/csrc/*.hip / *.hpp give a default under `#ifndef NAME` must be named
+    in the table of build switches of DESIGN.md section 4 (what it selects, who sets it).  Source text only: nothing is built."""
+    import glob
+    given_default = {}
+    for path in sorted(glob.glob(os.path.join(ROOT, "permutect_amd", "csrc", "*.hip")) + glob.glob(os.path.join(ROOT, "permutect_amd", "csrc", "*.hpp"))):
+        with open(path) as f:
+            text = f.read()
+        for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[^\n]*\n(?:[ \t]*(?://[^\n]*)?\n)*[ \t]*#[ \t]*define[ \t]+(\w+)", text, re.M):
+            if m.group(1) == m.group(2):
+                given_default.setdefault(m.group(1), os.path.basename(path))
+    assert {"PMT_RT", "PMT_FRAG_AHEAD", "PMT_SH_NTF", "PMT_DGRAD_PIECES", "PMT_BWD_TRACE", "C3_TRACE"} <= set(given_default), given_default  # (the scan works)
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        design = f.read()
+    start = design.index("**Build switches.**")
+    rows = [line for line in design[start:design.index("\n## ", start)].splitlines() if line.startswith("|")]
+    assert len(rows) > 2, "the table of build switches"
+    listed = {name for row in rows[2:] for name in re.findall(r"`(\w+)`", row.split("|")[1])}
+    missing = {name: where for name, where in given_default.items() if name not in listed}
+    assert not missing, f"switches without a row in DESIGN.md's table of build switches: {missing}"
