@@ -311,6 +311,12 @@ int pmt_abi_version(void);
 #define PMT_FORCE_FWD_BF16X3 5     /* the exact-width FORWARD on three bf16 pieces; auto otherwise   */
 int pmt_shape_info(int32_t* nine);
 int pmt_shape_id(const struct PmtModel* m);
+/* The shape a model WOULD fill, whatever this build's: nine = (NTF, NTR, NTD, NTE, F, R, D, H, E) and PMT_OK when some build of the
+ * library can run the model on tile-exact instances -- the read MLP starts and the reducer ends with a Linear, each keeps one tile
+ * count in between, no skip block is deeper than two layers, no tile count exceeds eight -- else PMT_E_UNSUPPORTED (the generic
+ * instance).  The same in every build (pmt_host.hip); pmt_shape_id compares its result with pmt_shape_info, and
+ * permutect_amd/engine/instances.py names the library to pick or build after it. */
+int pmt_model_shape(const struct PmtModel* m, int32_t* nine);
 /* The compile-time limits of THIS build of the library: four[0] widest register-resident activation (PMT_MAX_WIDTH: 64; the wide
  * build `libpermutect_amd_wide.so` -- csrc/Makefile `make wide`, generic instances only -- 128), [1] largest d_ffn / 2, [2] floats of
  * one stash slot, [3] waves per workgroup of the read-set kernels.  permutect_amd/engine/instances.py loads the wide build for a
@@ -657,7 +663,8 @@ int pmt_posterior_rows(const float* float_rows, int64_t float_stride, int32_t n_
                        const float* features_be, int32_t e, const int64_t* dest_ids, int32_t n, float* block, int64_t block_stride,
                        void* stream);
 
-/* Partition variants into register-resident groups: greedy over consecutive variants so that each group has
+/* The group planners (csrc/pmt_plan.hip; the packing rule they all share: csrc/pmt_plan.hpp).
+ * Partition variants into register-resident groups: greedy over consecutive variants so that each group has
  * <= PMT_GROUP_MAX_SETS sets and its tiles fit the workgroup: ref tiles and alt tiles go to disjoint waves, two per wave,
  * i.e. ceil(ceil(ref/16) / 2) + ceil(ceil(alt/16) / 2) <= PMT_GROUP_WAVES (so never more than PMT_GROUP_TILES tiles).  Counts are HOST arrays
  * (upper bounds are fine: a DownsampledBatch reuses its parent's plan).  group_start / group_tile_base must hold

@@ -719,7 +719,7 @@ struct GroupGeom {
 };
 
 // A group fits a workgroup when its ref tiles and its alt tiles can be dealt to disjoint sets of waves, PMT_RT per wave
-// (the planner, pmt_plan_groups, packs with the same rule).
+// (the planners pack by the same rule on READ counts, pmt_plan.hpp; this one stays on tiles: translation units override PMT_RT / PMT_WAVES).
 DEV bool group_fits(int tiles_ref, int tiles_alt) {
     return (tiles_ref + PMT_RT - 1) / PMT_RT + (tiles_alt + PMT_RT - 1) / PMT_RT <= PMT_WAVES;
 }
@@ -891,7 +891,7 @@ DEV void drop_apply(const PmtDrop& d, int lin, f4 (&y)[PMT_RT][NT], int g) {
     }
 }
 
-extern "C" int pmt_stash_slots(const PmtModel* m);  // host helper (pmt_host.hip)
+extern "C" int pmt_stash_slots(const PmtModel* m);  // host helper (pmt_host.hip, beside pmt_stash_bytes)
 extern "C" int pmt_shape_id(const PmtModel* m);     // host: the instance a model runs (permutect_amd.h: PMT_SHAPE_*)
 // A batch that brings a dropout seed to a model with dropout_p > 0 runs an instance that carries the masks: ShapeP0XD (the
 // production shape, one-launch path only), else the generic instance.

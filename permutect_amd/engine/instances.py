@@ -40,37 +40,15 @@ def cache_dir() -> Optional[str]:
     return os.environ.get("PMT_INSTANCE_DIR") or None
 
 
-def _tiles(n: int) -> int:
-    return (n + 15) // 16
-
-
 def exact_shape_of(desc: L.PmtModel) -> Optional[Tuple[int, ...]]:
-    """(NTF, NTR, NTD, NTE, F, R, D, H, E) if SOME build of the library can run the model on tile-exact instances -- the conditions of
-    pmt_shape_id (pmt_host.hip) with the tile counts left open -- else None."""
-    rm, red = desc.read_mlp, desc.reducer
-    if rm.n_ops < 1 or red.n_ops < 1:
+    """(NTF, NTR, NTD, NTE, F, R, D, H, E) if SOME build of the library can run the model on tile-exact instances (pmt_model_shape,
+    csrc/pmt_host.hip: the conditions of pmt_shape_id with the tile counts left open; the same in every build) -- else None."""
+    nine = (C.c_int32 * 9)()
+    rc = L.load().pmt_model_shape(C.byref(desc), nine)
+    if rc == L.E_UNSUPPORTED:
         return None
-    first, last = rm.ops[0], red.ops[red.n_ops - 1]
-    if first.kind != L.OP_LINEAR or last.kind != L.OP_LINEAR:
-        return None
-    lf, ll = desc.lin[first.lin[0]], desc.lin[last.lin[0]]
-    ntf, ntr, ntd, nte = _tiles(desc.num_read_features), _tiles(lf.out_dim), _tiles(desc.d_model), _tiles(desc.feature_dim)
-
-    def ops_fill(mlp, lo, hi, nt):
-        for i in range(lo, hi):
-            o = mlp.ops[i]
-            if o.kind == L.OP_SKIP and o.n_layers > 2:  # (skip blocks of three and four layers run the generic instances: pmt_shape_id)
-                return False
-            for k in range(o.n_layers if o.kind == L.OP_SKIP else 1):
-                ln = desc.lin[o.lin[k]]
-                if _tiles(ln.in_dim) != nt or _tiles(ln.out_dim) != nt:
-                    return False
-        return True
-    ok = (_tiles(lf.in_dim) == ntf and ops_fill(rm, 1, rm.n_ops, ntr) and _tiles(desc.read_embed_dim) == ntr and desc.d_ffn >= 2
-          and ops_fill(red, 0, red.n_ops - 1, ntd) and _tiles(ll.in_dim) == ntd and _tiles(ll.out_dim) == nte)
-    if not ok or max(ntf, ntr, ntd, nte) > 8:  # (more than four tiles: built with the wide build's 8-tile register arrays, csrc/Makefile)
-        return None
-    return (ntf, ntr, ntd, nte, desc.num_read_features, lf.out_dim, desc.d_model, desc.d_ffn // 2, desc.feature_dim)
+    L.check(rc, "pmt_model_shape")
+    return tuple(int(v) for v in nine)
 
 
 class _BuildLock:
@@ -175,8 +153,8 @@ def build_instance(shape, log=print) -> Optional[str]:
 
 
 def widest_layer(desc: L.PmtModel) -> int:
-    """the widest activation of the read-set kernels and the row MLPs behind their inputs (what PMT_MAX_WIDTH bounds: pmt_host.hip,
-    pmt_model_check)"""
+    """the widest activation of the read-set kernels and the row MLPs behind their inputs (what PMT_MAX_WIDTH bounds: pmt_model_check,
+    csrc/pmt_host.hip)"""
     w = max(desc.num_read_features, desc.d_model, desc.feature_dim)
     for i in range(desc.n_linear):
         w = max(w, desc.lin[i].out_dim)

@@ -220,7 +220,7 @@ class PmtPruneStats(C.Structure):
 
 PRUNE_NO_ARTIFACT, PRUNE_NO_NONARTIFACT, PRUNE_CONFUSION_COLUMN, PRUNE_RATES_SUM_TO_ONE, PRUNE_LEVEL_RANGE = 1, 2, 4, 8, 16
 
-EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", "pmt_limits", "pmt_struct_bytes", "pmt_model_check", "pmt_plan_groups", "pmt_plan_groups_device", "pmt_plan_device_chunks", "pmt_stash_bytes", "pmt_pack_params",
+EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", "pmt_model_shape", "pmt_limits", "pmt_struct_bytes", "pmt_model_check", "pmt_plan_groups", "pmt_plan_groups_device", "pmt_plan_device_chunks", "pmt_stash_bytes", "pmt_pack_params",
            "pmt_scan_counts", "pmt_forward", "pmt_backward", "pmt_clip_adamw",
            "pmt_dropout_mask", "pmt_rows_stash_bytes", "pmt_rows_forward", "pmt_rows_backward", "pmt_rows_workspace_floats", "pmt_cnn_forward", "pmt_cnn_backward", "pmt_cnn_stash_floats", "pmt_cnn_workspace_floats",
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
@@ -345,6 +345,7 @@ def load(path: str = None) -> C.CDLL:
                            f"({lib.pmt_struct_bytes(which)} B)")
     lib.pmt_shape_info.argtypes = [P(i32)]
     lib.pmt_shape_id.argtypes = [P(PmtModel)]
+    lib.pmt_model_shape.argtypes = [P(PmtModel), P(i32)]
     lib.pmt_build_id.argtypes = [C.c_char_p, i32]
     # the planner's constants below are this module's; the kernels' are the library's: they must be the same numbers
     if limits_of(lib)["group_waves"] != GROUP_WAVES:

@@ -115,6 +115,44 @@ def test_device_planner_is_the_host_planner_chunk_by_chunk(n):
         assert int(fault.item()) == 4 and int(ng.item()) == g - 1
 
 
+@pytest.mark.parametrize("n", [64, 65, 257, 320])
+@pytest.mark.parametrize("counts", ["sets64", "full", "oversized"])
+def test_device_planner_shares_the_host_planners_rule_at_its_limits(n, counts):
+    """pmt_plan_groups_device and pmt_plan_groups pack by one rule (csrc/pmt_plan.hpp), chunk by chunk: where groups close on the 64-set
+    limit alone (sets of one alt read), where one set fills every wave ((128, 128) reads), and with a set beyond one workgroup
+    ((300, 300) at index 70 of WGS-shaped counts), which must raise PMT_FAULT_PLAN with the group count inside the capacity."""
+    from permutect_amd.engine import lib as L
+    lib, chunk = L.load(), 256
+    rng = np.random.default_rng(n)
+    ref, alt = {"sets64": (np.zeros(n), np.ones(n)), "full": (np.full(n, 128), np.full(n, 128)),
+                "oversized": (rng.integers(0, 11, n), rng.integers(1, 16, n))}[counts]
+    ref, alt = ref.astype(np.int32), alt.astype(np.int32)
+    if counts == "oversized" and n > 70:
+        ref[70] = alt[70] = 300
+    chunks = lib.pmt_plan_device_chunks(n)
+    capacity = n + chunks  # (never more groups than sets)
+    ro = torch.from_numpy(np.concatenate([[0], np.cumsum(ref)]).astype(np.int32)).to(DEV)
+    ao = torch.from_numpy(np.concatenate([[0], np.cumsum(alt)]).astype(np.int32)).to(DEV)
+    gs = torch.full((capacity + 1,), -1, dtype=torch.int32, device=DEV)
+    gt = torch.full((capacity + 1,), -1, dtype=torch.int32, device=DEV)
+    ng, fault = torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    scratch = torch.empty(2 * chunks, dtype=torch.int32, device=DEV)
+    L.check(lib.pmt_plan_groups_device(ro.data_ptr(), ao.data_ptr(), n, gs.data_ptr(), gt.data_ptr(), capacity, ng.data_ptr(), fault.data_ptr(),
+                                       scratch.data_ptr(), torch.cuda.current_stream().cuda_stream), "pmt_plan_groups_device")
+    torch.cuda.synchronize()
+    g = int(ng.item())
+    if counts == "oversized" and n > 70:
+        assert int(fault.item()) == 4 and 0 < g <= capacity
+        return
+    want_gs, want_gt = [0], [0]
+    for lo in range(0, n, chunk):
+        hs, ht = _host_plan(ref[lo:lo + chunk], alt[lo:lo + chunk])
+        want_gs += [lo + int(v) for v in hs[1:]]
+        want_gt += [want_gt[-1] + int(v) for v in ht[1:]]
+    assert int(fault.item()) == 0 and g == len(want_gs) - 1
+    assert gs[: g + 1].cpu().tolist() == want_gs and gt[: g + 1].cpu().tolist() == want_gt
+
+
 def test_a_downsampled_training_step_on_its_own_plan_equals_the_step_on_its_parents(monkeypatch):
     """The same DownsampledBatch through forward, losses and backward on the device-made plan of ITS counts and (PMT_DEVICE_PLAN=0) on its
     parent's plan as rounds 1 - 4 ran it: the same logits and gradients up to the order of the float atomics -- from about half the

@@ -1,4 +1,4 @@
-"""The read-set backward's bias gradients through the padding column of dW (pmt_bwd_device.hpp: PMT_BC_OF; pmt_host.hip: the emit
+"""The read-set backward's bias gradients through the padding column of dW (pmt_bwd_device.hpp: PMT_BC_OF; pmt_pack.hip: the emit
 table's column in_dim).  The exact-width instances stage 1.0 at feature position in_dim of a linear's input, so that column in_dim of
 the weight-gradient block IS the bias gradient, and the emit table sends it to the bias.  What can go wrong: the 1.0 in the wrong
 lane / register / tile, a column that lands beside the bias or in a weight, a side without tiles, sums across groups and the fold of
