@@ -493,6 +493,46 @@ int pmt_posterior_step(const PmtPosteriorRows* rows, int64_t first, int64_t coun
  * PMT_E_INVALID.  count == 0: PMT_OK, nothing written. */
 int pmt_posterior_update(const float* partials, int32_t num_partial_rows, int64_t count, float* raw, float* adam_m, float* adam_v, int64_t step,
                          double lr, double beta1, double beta2, double eps, float* totals_tc, double* loss_sum, void* stream);
+/* pmt_posterior_step with the E step of the context-dependent SNV priors in the same pass (reference posterior_model_priors.py:116-123,
+ * `increment_somatic_snv_context_totals_rrra`): the same kernel body under a compile-time flag, the same arguments, the same `partials`
+ * bit for bit, and for every row of variant type 0 (SNV, after the clamp above) llrintf(p_somatic * 2^30) -- p_somatic the row's float
+ * posterior of the somatic call, the value that goes into totals[0][0] -- added into somatic_snv_fixed_rrra[context] (625 bins, the
+ * caller zeroes them before an epoch) with a 64-bit integer vector atomic.  Integer adds commute: the bins are the same bits from run to
+ * run and for any num_partial_rows, without a second pass.  A bin holds at most rows * 2^30: fewer than 2^33 SNV rows per epoch.  A
+ * context outside 0 .. 624 is clamped like everywhere else, so nothing is added outside the 625 bins.  The number of SNV rows per bin
+ * (the reference's snv_context_totals_rrra) is data alone and the caller's to count.
+ * Invalid as pmt_posterior_step, or somatic_snv_fixed_rrra NULL: PMT_E_INVALID, nothing launched. */
+#define PMT_CONTEXT_FIXED_ONE (1ll << 30)
+int pmt_posterior_step_context(const PmtPosteriorRows* rows, int64_t first, int64_t count, const PmtPosteriorParams* params, float* partials,
+                               int32_t num_partial_rows, unsigned long long* somatic_snv_fixed_rrra, void* stream);
+
+/* The M step of the context-dependent SNV priors (reference posterior_model_priors.py:158-222) as ONE persistent launch of one
+ * wavefront.  The reference fits its generative model of per-context mutation rates by pymc's mean-field ADVI and reports the mean of
+ * 1000 draws: stochastic, unseeded, not reproducible.  This is a DETERMINISTIC estimator of the SAME generative model, not ADVI, and
+ * claims no parity with ADVI's numbers: the maximiser of the model's log joint with every prior density taken in its unconstrained
+ * coordinate (logit for the Beta, log for the Gammas, softmax basis for the Dirichlets), in which the mode of each conjugate piece is
+ * its posterior mean.
+ *   cells: substitution s = 0 .. 11 (ref * 4 + alt without the four ref == alt entries, A>C = 0 .. T>G = 11), flanks c = left * 4 + right;
+ *   cell (s, c) is rrra[left][ref][right][alt] of the 5 x 5 x 5 x 5 tables (bins with a deletion code, index 4, are dropped).
+ *   k_sc = rint(somatic_snv_fixed_rrra / 2^30) and n_sc = rint(snv_context_totals_rrra + ratio * sum(totals_tc) / 64), both in float
+ *   (to even), as the reference rounds its float32 totals (:158-171); k is capped at n.
+ *   unknowns (207): u, R = sigmoid(u); a = log kappa_s, b = log kappa_c; x[12], theta_s = softmax(x); y[12][16], theta_s. = softmax(y[s]);
+ *   rate p_sc = R 12 theta_s 16 theta_sc, log p capped at log(1 - 1e-6).
+ *   F = sum_sc [k log p + (n - k) log(1 - p)] + log R + 1e6 log(1 - R) + 4 a - 5 kappa_s + 4 b - 5 kappa_c
+ *     + lgamma(12 kappa_s) - 12 lgamma(kappa_s) + kappa_s sum_s log theta_s + 12 (lgamma(16 kappa_c) - 16 lgamma(kappa_c)) + kappa_c sum_sc log theta_sc
+ *   (Beta(1, 1e6), Gamma(4, 5) twice, Dirichlet(kappa_s 1_12), twelve Dirichlet(kappa_c 1_16), Binomial), maximised by `steps` steps of
+ *   torch.optim.Adam on -F / max(sum k, 1) from x = y = 0, a = b = log 0.8, u = logit((sum k + 1) / (sum n + 1e6 + 1)) with the learning
+ *   rate lr0 (1 - t / steps) at step t = 0 .. steps - 1 (fresh moments, no weight decay).  Only the analytic gradient is evaluated.
+ *   snv_log_priors_rrra [625]: log p_sc of the last iterate into the 192 SNV entries; the other 433 keep their bits.
+ *   diagnostics [PMT_CONTEXT_FIT_DIAG] (may be NULL): 0 the last step's largest |dF / d unknown| / max(sum k, 1) (what Adam saw), 1 sum k,
+ *   2 kappa_s, 3 kappa_c, then n_sc [12][16] and k_sc [12][16] as the kernel rounded them.
+ * Everything is read on the device (nothing is read back); no LDS, no barrier, no atomics: run-to-run bit-identical.  A cell with
+ * n = 0, all k = 0 and ratio = 0 are ordinary inputs.  A NULL array other than diagnostics, steps < 1 or > PMT_FIT_MAX_STEPS, lr0 or
+ * ratio negative or not finite, lr0 == 0: PMT_E_INVALID, nothing launched. */
+#define PMT_CONTEXT_FIT_DIAG (4 + 2 * 192)
+int pmt_context_priors_fit(const unsigned long long* somatic_snv_fixed_rrra, const int64_t* snv_context_totals_rrra, const float* totals_tc,
+                           double ratio, float* snv_log_priors_rrra, int32_t steps, double lr0, double beta1, double beta2, double eps,
+                           float* diagnostics, void* stream);
 
 /* Per-variant losses (reference architecture/artifact_model.py:267-325). */
 typedef struct PmtLossArgs {

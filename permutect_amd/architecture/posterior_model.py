@@ -12,6 +12,12 @@ Where it runs decides how:
     (csrc/pmt_posterior.hip): two launches per minibatch on one stream, nothing read back before the last epoch has been enqueued;
   * a model on the CPU, a model that is not float32, or any model under PMT_POSTERIOR=torch runs the torch mirror: autograd and
     torch.optim.Adam(self.spectra.parameters(), lr), nothing clipped.
+
+Context-dependent SNV priors are opt-in (`learn_priors_and_spectra(..., context_dependent_snv_priors=True)`): the reference's regime
+(context on for the second half of the epochs, the 5 x 5 x 5 x 5 table refitted after each of them), with the table's fit replaced by a
+deterministic estimator of the same generative model -- the reference's own fit is a stochastic, unseeded pymc ADVI run and is NOT
+reproduced; see architecture/posterior_priors.py.  On the device the E step adds the somatic mass per context in the same pass
+(pmt_posterior_step_context, integer atomics: bit-reproducible) and the M step is one persistent launch (pmt_context_priors_fit).
 """
 from __future__ import annotations
 
@@ -203,21 +209,36 @@ class PosteriorModel(nn.Module):
 
     # ---- learning --------------------------------------------------------------------------------------------------------------
     def learn_priors_and_spectra(self, posterior_data: PosteriorRows, num_iterations: int, ignored_to_non_ignored_ratio: float,
-                                 learning_rate: float = 0.001, batch_size: int = 64) -> List[float]:
+                                 learning_rate: float = 0.001, batch_size: int = 64, context_dependent_snv_priors: bool = False,
+                                 context_fit_steps: int = 2000, context_fit_lr: float = 0.05) -> List[float]:
         """Reference :101-165.  Per epoch an E step over the minibatches -- an Adam step on minus the mean log evidence each, the
-        posteriors added into totals by variant type and call -- then the M step of the priors.  Context dependence stays OFF in every
-        epoch (the reference's regime for the first half of its epochs): its context M step, a pymc ADVI fit, is not built.  Returns the
-        mean negative log evidence of every epoch; `self.last_posterior_totals_tc` keeps the last epoch's totals."""
-        if num_iterations < 0 or batch_size < 1:
-            raise ValueError(f"learn_priors_and_spectra: num_iterations {num_iterations}, batch_size {batch_size}")
+        posteriors added into totals by variant type and call -- then the M step of the priors.  Returns the mean negative log evidence
+        of every epoch; `self.last_posterior_totals_tc` keeps the last epoch's totals.
+
+        By default context dependence stays OFF in every epoch (the reference's regime for the first half of its epochs).  With
+        `context_dependent_snv_priors` the reference's regime is followed exactly: context is on for 1-based epoch e > num_iterations / 2
+        (with one iteration: from the start), the E step of such an epoch also accumulates the somatic SNV mass and the SNV count per
+        context, its M step refits `somatic_snv_log_priors_rrra`, and the flag stays on afterwards, so thresholds and calls use the
+        table.  The table's fit is the deterministic estimator of architecture/posterior_priors.py (`context_fit_steps` Adam steps at
+        `context_fit_lr`, decaying to zero), NOT the reference's ADVI; `self.priors.last_context_fit` keeps the last fit's diagnostics."""
+        if num_iterations < 0 or batch_size < 1 or context_fit_steps < 1 or not context_fit_lr > 0:
+            raise ValueError(f"learn_priors_and_spectra: num_iterations {num_iterations}, batch_size {batch_size}, context fit "
+                             f"{context_fit_steps} steps at {context_fit_lr}")
         self.priors.disable_context_dependent_snv_priors()
+        self.priors.context_fit_steps, self.priors.context_fit_lr = int(context_fit_steps), float(context_fit_lr)
         if self._on_device():
-            return self._learn_on_device(posterior_data, num_iterations, ignored_to_non_ignored_ratio, learning_rate, batch_size)
+            return self._learn_on_device(posterior_data, num_iterations, ignored_to_non_ignored_ratio, learning_rate, batch_size,
+                                         context_dependent_snv_priors)
         dtype, dev = self.priors.log_priors_vc.dtype, self.priors.log_priors_vc.device
         optimizer = torch.optim.Adam(self.spectra.parameters(), lr=learning_rate)
         n = len(posterior_data)
         losses = []
-        for _ in range(num_iterations):
+        for epoch in range(1, num_iterations + 1):
+            context = context_dependent_snv_priors and epoch > num_iterations / 2
+            if context:
+                self.priors.enable_context_dependent_snv_priors()
+                somatic_snv_totals_rrra = PosteriorModelPriors.initialize_snv_context_totals_rrra(dev, dtype)
+                snv_context_totals_rrra = PosteriorModelPriors.initialize_snv_context_totals_rrra(dev, dtype)
             loss_sum = 0.0
             posterior_totals_tc = torch.zeros((len(Variation), len(Call)), device=dev, dtype=dtype)
             for first in range(0, n, batch_size):
@@ -225,18 +246,27 @@ class PosteriorModel(nn.Module):
                 relative_posteriors = self.log_relative_posteriors_bc(batch)
                 log_evidence = torch.logsumexp(relative_posteriors, dim=1)
                 posteriors_bc = torch.softmax(relative_posteriors, dim=-1).detach()
+                if context:
+                    PosteriorModelPriors.increment_somatic_snv_context_totals_rrra(somatic_snv_totals_rrra, snv_context_totals_rrra, batch,
+                                                                                   posteriors_bc)
                 posterior_totals_tc.index_add_(dim=0, index=batch.variant_types.long(), source=posteriors_bc)
                 loss = -torch.mean(log_evidence)
                 optimizer.zero_grad(set_to_none=True)
                 loss.backward()
                 optimizer.step()
                 loss_sum += len(batch) * loss.detach().item()
-            self.priors.update_priors_m_step(posterior_totals_tc, ignored_to_non_ignored_ratio)
+            if context:
+                self.priors.update_priors_m_step(posterior_totals_tc, ignored_to_non_ignored_ratio, somatic_snv_totals_rrra,
+                                                 snv_context_totals_rrra)
+                self.last_somatic_snv_totals_rrra, self.last_snv_context_totals_rrra = somatic_snv_totals_rrra, snv_context_totals_rrra
+            else:
+                self.priors.update_priors_m_step(posterior_totals_tc, ignored_to_non_ignored_ratio)
             self.last_posterior_totals_tc = posterior_totals_tc
             losses.append(loss_sum / n if n else float("nan"))
         return losses
 
-    def _learn_on_device(self, data: PosteriorRows, num_iterations: int, ratio: float, lr: float, batch_size: int) -> List[float]:
+    def _learn_on_device(self, data: PosteriorRows, num_iterations: int, ratio: float, lr: float, batch_size: int,
+                         context_dependent_snv_priors: bool = False) -> List[float]:
         dev = self.priors.log_priors_vc.device
         assert data.device == dev, (data.device, dev)
         n = len(data)
@@ -248,19 +278,37 @@ class PosteriorModel(nn.Module):
         loss_sums = torch.zeros(max(num_iterations, 1), dtype=torch.float64, device=dev)
         lib, rows, step = L.load(), data.descriptor(), 0
         (beta1, beta2), eps = ADAM_DEFAULTS["betas"], ADAM_DEFAULTS["eps"]  # (the learning rate is the caller's)
+        context_epochs = [e for e in range(1, num_iterations + 1) if context_dependent_snv_priors and e > num_iterations / 2]
+        if context_epochs:
+            # the somatic mass per context bin of every context epoch, in 2^-30 fixed point (pmt_posterior_step_context), and the SNV rows
+            # per bin: data alone, counted once
+            fixed = torch.zeros(len(context_epochs), 625, dtype=torch.int64, device=dev)
+            snv_counts = PosteriorModelPriors.snv_context_counts_rrra(data)
         with torch.cuda.device(dev), torch.no_grad():
             stream = L.raw_stream(dev)
             for epoch in range(num_iterations):
+                context = (epoch + 1) in context_epochs
+                if context:
+                    self.priors.enable_context_dependent_snv_priors()
+                    fixed_epoch = fixed[context_epochs.index(epoch + 1)]
                 keep: list = []
                 params = self._params_descriptor(raw, keep)  # (the priors' storage: the M step below writes it in place)
                 for first in range(0, n, batch_size):
                     count, step = min(batch_size, n - first), step + 1
-                    L.check(lib.pmt_posterior_step(C.byref(rows), first, count, C.byref(params), partials.data_ptr(), num_partial_rows, stream),
-                            "pmt_posterior_step")
+                    if context:
+                        L.check(lib.pmt_posterior_step_context(C.byref(rows), first, count, C.byref(params), partials.data_ptr(), num_partial_rows,
+                                                               fixed_epoch.data_ptr(), stream), "pmt_posterior_step_context")
+                    else:
+                        L.check(lib.pmt_posterior_step(C.byref(rows), first, count, C.byref(params), partials.data_ptr(), num_partial_rows, stream),
+                                "pmt_posterior_step")
                     L.check(lib.pmt_posterior_update(partials.data_ptr(), num_partial_rows, count, raw.data_ptr(), adam_m.data_ptr(),
                                                      adam_v.data_ptr(), step, lr, beta1, beta2, eps,
                                                      totals[epoch].data_ptr(), loss_sums[epoch:].data_ptr(), stream), "pmt_posterior_update")
-                self.priors.update_priors_m_step(totals[epoch], ratio)
+                if context:
+                    self.priors.update_priors_m_step(totals[epoch], ratio, fixed_epoch, snv_counts)
+                    self.last_somatic_snv_totals_rrra, self.last_snv_context_totals_rrra = fixed_epoch.view(5, 5, 5, 5), snv_counts
+                else:
+                    self.priors.update_priors_m_step(totals[epoch], ratio)
             self.load_raw_spectra_parameters(raw)  # the fitted raw values back into the module
             if num_iterations:
                 self.last_posterior_totals_tc = totals[num_iterations - 1]

@@ -1,5 +1,5 @@
 // The posterior model's per-candidate evaluation and the minibatch fit of its spectra (include/permutect_amd.h: pmt_posterior_forward,
-// pmt_posterior_step, pmt_posterior_update; the torch form this was written from: permutect_amd/architecture/posterior_model.py,
+// pmt_posterior_step, pmt_posterior_step_context, pmt_posterior_update; the torch form this was written from: permutect_amd/architecture/posterior_model.py,
 // posterior_spectra.py, posterior_priors.py; reference architecture/posterior_model.py:69-157).
 //
 // A lane per candidate, workgroups of one wavefront.  Per candidate (48 bytes in):
@@ -21,6 +21,10 @@
 // then output thread o adds, in lane order 0 .. 63, the values of the lanes whose key is o's cell into a register it keeps across the
 // grid-stride loop.  No atomics, no workgroup waits for another; the second launch (pmt_posterior_update, one workgroup) adds the rows
 // in row order and applies Adam.
+//
+// pmt_posterior_step_context is the same kernel body with one addition for the context-dependent SNV priors' E step: every SNV row
+// adds llrintf(p_somatic 2^30) into its context's 64-bit bin with an integer atomic.  Integer adds commute, so the 625 bins are the same
+// bits from run to run and for any grid -- this file's rule kept without a second pass; `partials` do not change by a bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -306,9 +310,11 @@ __device__ __forceinline__ void po_output_map(int o, int& value, int& key, int& 
     else { value = 0; key = -2; cell = 0; }
 }
 
-__global__ __launch_bounds__(PO_WAVE) void pmt_posterior_step_kernel(PmtPosteriorRows rows, long long first, long long count, PmtPosteriorParams P,
-                                                                    float* __restrict__ partials) {
-    __shared__ PoShared sh;
+// CONTEXT: every SNV row also adds its somatic posterior, in 2^-30 fixed point, into its context's bin (pmt_posterior_step_context).
+// Integer adds commute, so the bins do not depend on the order the workgroups arrive in; everything else is the same code.
+template <bool CONTEXT>
+__device__ __forceinline__ void po_step(PoShared& sh, const PmtPosteriorRows& rows, long long first, long long count, const PmtPosteriorParams& P,
+                                        float* __restrict__ partials, unsigned long long* __restrict__ somatic_snv_fixed_rrra) {
     po_prepare(sh, P.raw);
     const int lane = threadIdx.x;
     float acc[2] = {0.f, 0.f};
@@ -324,6 +330,10 @@ __global__ __launch_bounds__(PO_WAVE) void pmt_posterior_step_kernel(PmtPosterio
             const PoRow w = po_load(rows, first + base + lane);
             PoOut o;
             po_row<true>(w, sh, P, o, v, keys);
+            if (CONTEXT && w.type == 0) {  // (w.ctx is clamped into 0 .. 624: po_load)
+                const long long q = llrintf(v[16 + PO_SOMATIC] * (float)PMT_CONTEXT_FIXED_ONE);
+                if (q > 0) atomicAdd(somatic_snv_fixed_rrra + w.ctx, (unsigned long long)q);
+            }
         }
         for (int j = 0; j < PO_VALUES; ++j) sh.values[lane][j] = v[j];
         for (int j = 0; j < 3; ++j) sh.keys[lane][j] = keys[j];
@@ -343,6 +353,19 @@ __global__ __launch_bounds__(PO_WAVE) void pmt_posterior_step_kernel(PmtPosterio
     float* out = partials + (size_t)blockIdx.x * PMT_POSTERIOR_PARTIAL;
     out[lane] = acc[0] * scale;
     out[lane + PO_WAVE] = lane + PO_WAVE < PMT_POSTERIOR_RAW ? acc[1] * scale : acc[1];
+}
+
+__global__ __launch_bounds__(PO_WAVE) void pmt_posterior_step_kernel(PmtPosteriorRows rows, long long first, long long count, PmtPosteriorParams P,
+                                                                    float* __restrict__ partials) {
+    __shared__ PoShared sh;
+    po_step<false>(sh, rows, first, count, P, partials, nullptr);
+}
+
+__global__ __launch_bounds__(PO_WAVE) void pmt_posterior_step_context_kernel(PmtPosteriorRows rows, long long first, long long count,
+                                                                            PmtPosteriorParams P, float* __restrict__ partials,
+                                                                            unsigned long long* __restrict__ somatic_snv_fixed_rrra) {
+    __shared__ PoShared sh;
+    po_step<true>(sh, rows, first, count, P, partials, somatic_snv_fixed_rrra);
 }
 
 __global__ __launch_bounds__(PMT_POSTERIOR_PARTIAL) void pmt_posterior_update_kernel(const float* __restrict__ partials, int num_partial_rows,
@@ -396,6 +419,17 @@ extern "C" int pmt_posterior_step(const PmtPosteriorRows* rows, int64_t first, i
     if (count == 0) return PMT_OK;
     hipLaunchKernelGGL(pmt_posterior_step_kernel, dim3((unsigned)num_partial_rows), dim3(PO_WAVE), 0, reinterpret_cast<hipStream_t>(stream), *rows,
                        (long long)first, (long long)count, *params, partials);
+    return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
+}
+
+extern "C" int pmt_posterior_step_context(const PmtPosteriorRows* rows, int64_t first, int64_t count, const PmtPosteriorParams* params,
+                                          float* partials, int32_t num_partial_rows, unsigned long long* somatic_snv_fixed_rrra, void* stream) {
+    const int rc = po_check(rows, first, count, params);
+    if (rc != PMT_OK) return rc;
+    if (!partials || num_partial_rows < 1 || !somatic_snv_fixed_rrra) return PMT_E_INVALID;
+    if (count == 0) return PMT_OK;
+    hipLaunchKernelGGL(pmt_posterior_step_context_kernel, dim3((unsigned)num_partial_rows), dim3(PO_WAVE), 0, reinterpret_cast<hipStream_t>(stream),
+                       *rows, (long long)first, (long long)count, *params, partials, somatic_snv_fixed_rrra);
     return hipGetLastError() == hipSuccess ? PMT_OK : PMT_E_LAUNCH;
 }
 

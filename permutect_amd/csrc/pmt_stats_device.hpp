@@ -1,4 +1,5 @@
-// What the statistical kernels share (pmt_downsample_fit.hip, pmt_spectra_fit.hip, pmt_posterior.hip, pmt_prune.hip): torch.optim.Adam's update and
+// What the statistical kernels share (pmt_downsample_fit.hip, pmt_spectra_fit.hip, pmt_posterior.hip, pmt_context_fit.hip, pmt_prune.hip): torch.optim.Adam's
+// update and
 // its bias corrections, the sums over a wavefront, the fp32 digamma and the beta-binomial.  One definition each: the fits are pinned
 // by trajectory against float64 references, so a change here reaches all of them or none.  Every expression keeps its written order
 // of operations (plain fp32 / double, IEEE division and square root).
@@ -64,6 +65,19 @@ __device__ __forceinline__ float fit_sum32(float x) {
 __device__ __forceinline__ float fit_sum64(float x) {
     x = fit_sum16(x);
     return (fit_lane(x, 0) + fit_lane(x, 16)) + (fit_lane(x, 32) + fit_lane(x, 48));
+}
+
+// the largest value of each row of 16 lanes / of the 64 lanes (pmt_context_fit.hip: the softmax over a row, the largest gradient)
+__device__ __forceinline__ float fit_max16(float x) {
+    x = fmaxf(x, fit_dpp<0xB1>(x));
+    x = fmaxf(x, fit_dpp<0x4E>(x));
+    x = fmaxf(x, fit_dpp<0x141>(x));
+    x = fmaxf(x, fit_dpp<0x140>(x));
+    return x;
+}
+__device__ __forceinline__ float fit_max64(float x) {
+    x = fit_max16(x);
+    return fmaxf(fmaxf(fit_lane(x, 0), fit_lane(x, 16)), fmaxf(fit_lane(x, 32), fit_lane(x, 48)));
 }
 
 // the same in double (pmt_prune.hip): an xor butterfly, whose two addends at every level are the same pair in both lanes

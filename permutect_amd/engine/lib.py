@@ -28,6 +28,7 @@ OP_LINEAR, OP_SKIP = 0, 1
 SLOT_FLOATS = 4 * 256
 
 POSTERIOR_RAW, POSTERIOR_PARTIAL = 80, 128  # PMT_POSTERIOR_RAW, PMT_POSTERIOR_PARTIAL
+CONTEXT_FIXED_ONE, CONTEXT_FIT_DIAG = 1 << 30, 4 + 2 * 192  # PMT_CONTEXT_FIXED_ONE, PMT_CONTEXT_FIT_DIAG
 
 STEP_ON_DEVICE, STEP_SLOT = -1, 1000
 E_INVALID, E_UNSUPPORTED, E_CAPACITY, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4, -5
@@ -226,7 +227,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -320,6 +321,8 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_spectra_fit.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.pmt_posterior_forward.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, vp, vp, vp, vp]
     lib.pmt_posterior_step.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, i32, vp]
+    lib.pmt_posterior_step_context.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, i32, vp, vp]
+    lib.pmt_context_priors_fit.argtypes = [vp, vp, vp, C.c_double, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     lib.pmt_posterior_update.argtypes = [vp, i32, i64, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     lib.pmt_balance_step.argtypes = [P(PmtBalanceArgs), vp]
     lib.pmt_record_evaluation.argtypes = [P(PmtEvalArgs), vp, vp]

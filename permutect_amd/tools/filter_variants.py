@@ -9,12 +9,17 @@ in the same format.
 
 With `--genomic_span` the posterior stage follows (reference tools/filter_variants.py:244-289; architecture/posterior_model.py): rank 0
 turns the posterior data into device-resident columns, learns the priors and allele-fraction spectra
-(`PosteriorModel.learn_priors_and_spectra`; context-dependent SNV priors stay off in every epoch: the reference's pymc fit of them is not
-built), sets the error-probability threshold of every variant type and writes per-candidate probabilities, calls and the thresholds as
-arrays to `--calls_output` (.npz).  The artifact priors and spectra stored in the model file are loaded and, as in the reference
+(`PosteriorModel.learn_priors_and_spectra`), sets the error-probability threshold of every variant type and writes per-candidate
+probabilities, calls and the thresholds as arrays to `--calls_output` (.npz).  Context-dependent SNV priors stay off in every epoch
+unless `--context_dependent_snv_priors` is given: then the reference's regime runs (context on for the second half of the epochs, the
+5 x 5 x 5 x 5 table `priors.somatic_snv_log_priors_rrra` refitted after each of them and used for the thresholds and calls; it is part of
+the state_dict in the .npz).  The table's fit is a deterministic estimator of the reference's generative model of per-context mutation
+rates, one persistent launch on the device -- NOT the reference's stochastic pymc ADVI fit, whose numbers it does not claim to match
+(architecture/posterior_priors.py).  The artifact priors and spectra stored in the model file are loaded and, as in the reference
 (tools/filter_variants.py:242, :265), not used.
 
     ... --genomic_span 3e9 --calls_output calls.npz [--num_spectrum_iterations 10] [--germline_mode | --no_germline_mode] [--het_beta B]
+        [--context_dependent_snv_priors]
 
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N -m permutect_amd.tools.filter_variants ...`: WORLD_SIZE > 1) the
 candidates are cut into N contiguous shards, one process per GPU, no collective on the data path; rank 0 concatenates the shards'
@@ -97,13 +102,18 @@ def run_posterior_stage(args, posterior: MemoryMappedData, device, log=print):
     model = PosteriorModel(getattr(args, "initial_log_variant_prior"), getattr(args, "initial_log_artifact_prior"),
                            no_germline_mode=no_germline_mode, device=device, het_beta=getattr(args, "het_beta", None))
     ratio = (getattr(args, GENOMIC_SPAN_NAME) - n) / n
+    context = bool(getattr(args, "context_dependent_snv_priors", False))
     losses = model.learn_priors_and_spectra(rows, getattr(args, "num_spectrum_iterations"), ratio,
-                                            learning_rate=getattr(args, "spectrum_learning_rate"), batch_size=POSTERIOR_BATCH_SIZE)
+                                            learning_rate=getattr(args, "spectrum_learning_rate"), batch_size=POSTERIOR_BATCH_SIZE,
+                                            context_dependent_snv_priors=context)
     thresholds = model.calculate_probability_thresholds(rows, germline_mode=germline_mode, recall_weight=getattr(args, "recall_weight"))
     out = posterior_outputs(model, rows, thresholds, losses, germline_mode)
     np.savez(getattr(args, "calls_output"), **out)
     log(f"posterior model: {n} candidates, {len(losses)} epochs in {time.perf_counter() - t0:.3f} s; thresholds "
         f"{ {v.name: round(float(t), 4) for v, t in thresholds.items()} }; {int(out['filtered_b'].sum())} filtered")
+    if context and model.priors.last_context_fit is not None:
+        log(f"context-dependent SNV priors: the last fit's largest |dF / d unknown| / max(sum k, 1) = {model.priors.last_context_fit_max_grad():.3e} "
+            "(a deterministic estimator of the reference's model, not its ADVI fit)")
     return model, out
 
 
@@ -125,6 +135,9 @@ def parse_arguments(argv=None):
     parser.add_argument("--germline_mode", action="store_true", help="germline calls are not errors when the threshold is set")
     parser.add_argument("--no_germline_mode", action="store_true", help="no germline calls: somatic, artifact and sequencing error only")
     parser.add_argument("--het_beta", type=float, default=None, required=False, help="beta-binomial shape of the germline het spectrum instead of a binomial")
+    parser.add_argument("--context_dependent_snv_priors", action="store_true",
+                        help="learn the SNV prior per 3-base context and substitution in the second half of the epochs (a deterministic "
+                             "estimator of the reference's model, not its ADVI fit)")
     parser.add_argument("--recall_weight", type=float, default=1.0, required=False, help="weight of recall against precision in the F-beta score")
     args = parser.parse_args(argv)
     if posterior_stage_requested(args) and not args.calls_output:
