@@ -331,7 +331,7 @@ int pmt_build_id(char* out, int32_t capacity);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * 0 PmtModel, 1 PmtBatch, 2 PmtOutputs, 3 PmtOutputGrads, 4 PmtAdamW, 5 PmtLinear, 6 PmtOp, 7 PmtMlp, 8 PmtBlock, 9 PmtHead,
  * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs, 16 PmtPosteriorRows,
- * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats */
+ * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs */
 int pmt_struct_bytes(int which);
 
 /* Validates a descriptor against the kernels' limits. */
@@ -646,6 +646,57 @@ int pmt_prune_thresholds(const PmtPruneArgs* args, PmtPruneStats* stats, void* s
  * scatter).  NaN thresholds keep everything; `levels`, `label_art_frac` are not read.  n == 0: *kept_count = 0. */
 int pmt_prune_select(const PmtPruneArgs* args, float art_threshold, float nonart_threshold, int64_t* kept_ids, int64_t* kept_count,
                      void* scratch, void* stream);
+
+/* The worst offenders of an evaluation pass (reference training/model_training.py:232-268, :294-303): for every (true label, alt-count
+ * bin) the `queue_size` labeled variants that the model contradicts most confidently.  The reference walks `.tolist()` of every batch in
+ * Python, builds a Datum per row and keeps a PriorityQueue per key; here the queues are a TABLE in device memory and a batch is two
+ * launches.
+ *   A row is WRONG iff (label == 0 (artifact) and logit < 0) or (label == 1 (variant) and logit > 0): unlabeled rows, logit == 0 and NaN
+ *   logits never are.  Its confidence is |logit| (its fp32 bits order as the value: never zero, never NaN); its alt bin is
+ *   (alt_count - 1) / 3, UNCAPPED; its key is label * num_alt_keys + bin; its identity is (contig, position, ref code, alt code) from
+ *   columns 9 .. 15 of its int row: contig = column 9, the three others pairs of int16 decoded as the reference does,
+ *   65535 * (hi + 32768) + (lo + 32768) (reference data/datum.py:28,46-48: 65535, not 65536), in 32 bits.
+ *   THE ORDER of a key's slots: confidence descending, then contig (signed), position, ref code, alt code (unsigned) ascending.  Rows equal
+ *   in all five are kept as duplicates.  Each key keeps the first queue_size rows of that order of everything ever recorded.
+ * The table, 32-bit words (pmt_worst_table_bytes), K = 2 * num_alt_keys keys:
+ *   [0, 16) the header: words 0-1 (uint64) the WRONG rows whose alt bin lies outside [0, num_alt_keys) (counted, otherwise ignored),
+ *           word 2 (int32) the largest alt count of ANY row seen, word 3 zero, words 4-5 / 6-7 (uint64) the wrong rows of label 0 / 1
+ *           (those outside the table included), words 8-15 zero;
+ *   [16, 16 + K) the fill count of every key;
+ *   then [K][queue_size][5] the slots: confidence bits, contig, position, ref code, alt code.
+ * It is kept in CANONICAL FORM: every key's slots in the order above, unused slots zero -- so its bytes are a function of the MULTISET of
+ * recorded rows alone: the same for any grid, any arrival order, any cut of the rows into batches, and from run to run.  A table of
+ * zeros is the empty table. */
+typedef struct PmtWorstArgs {
+    int32_t num_variants, queue_size;          /* queue_size 1 .. PMT_WORST_MAX_QUEUE */
+    int32_t num_alt_keys, int_elem_bytes;      /* alt bins per label; bytes of an element of int_rows: 2, 4 or 8 */
+    PmtIntColumn labels, alt_counts;           /* alt_counts: the counts the model saw (a DownsampledBatch's own) */
+    const void* int_rows;                      /* element (i, c) at int_rows + (i * int_row_stride + c) elements; columns 9 .. 15 are read */
+    int64_t int_row_stride;
+    const float* logits_b;
+    int64_t scratch_bytes;                     /* what `scratch` holds: checked against pmt_worst_scratch_bytes(num_variants, ...) */
+} PmtWorstArgs;
+#define PMT_WORST_MAX_QUEUE 1024
+#define PMT_WORST_HEADER_WORDS 16
+size_t pmt_worst_table_bytes(int32_t queue_size, int32_t num_alt_keys);
+/* Bytes of the scratch of pmt_worst_record for batches of up to max_variants rows (0 for arguments out of range).  Its contents mean
+ * nothing between calls and need no initialisation. */
+size_t pmt_worst_scratch_bytes(int64_t max_variants, int32_t queue_size, int32_t num_alt_keys);
+/* Records one batch: TWO launches on `stream`, no memset, nothing waits for the device, no workgroup waits for another.
+ *   1. a grid over the rows: predicate, key, and ONE compare of the confidence bits against the key's current cut (its last slot, once
+ *      the key is full; a row equal to the cut goes on: identity may place it in front).  Each workgroup writes the survivors of its own
+ *      1024 rows, and their number, to its own segment of `scratch`; the header's counts by integer atomics.
+ *   2. a workgroup per key: gathers the key's survivors from every segment, sorts them with the kept slots in LDS (bitonic, the five-word
+ *      order above) -- in several passes of up to 2048 records when there are more, never truncating -- and writes the first queue_size
+ *      back in canonical form.  A key without survivors is left alone.
+ * num_variants == 0: PMT_OK, nothing launched.  queue_size outside 1 .. 1024: PMT_E_UNSUPPORTED.  A NULL pointer, num_variants < 0,
+ * num_alt_keys < 1, a column width other than 4 / 8 or a row element other than 2 / 4 / 8 bytes: PMT_E_INVALID.  scratch_bytes too
+ * small: PMT_E_WORKSPACE.  Nothing is launched in any of these cases. */
+int pmt_worst_record(const PmtWorstArgs* args, void* table, void* scratch, void* stream);
+/* table <- the table of the union of both multisets: ONE launch, a workgroup per key (both keys' slots sorted together in LDS), the
+ * header's counts added and its largest alt count the larger.  `other` is only read and must not be `table` (PMT_E_INVALID); `scratch`
+ * is not used and may be NULL. */
+int pmt_worst_merge(void* table, const void* other, int32_t queue_size, int32_t num_alt_keys, void* scratch, void* stream);
 
 /* The tallies of an evaluation step (reference metrics/evaluation_metrics.py:49-66 -> AccuracyMetrics, metrics/loss_metrics.py:226-243;
  * training/model_training.py:204-228 runs it three times per parent batch after every validation epoch): the weights of the LABELED

@@ -42,6 +42,7 @@ extern "C" int pmt_struct_bytes(int which) {
         case 17: return (int)sizeof(PmtPosteriorParams);
         case 18: return (int)sizeof(PmtPruneArgs);
         case 19: return (int)sizeof(PmtPruneStats);
+        case 20: return (int)sizeof(PmtWorstArgs);
         default: return PMT_E_INVALID;
     }
 }

@@ -218,6 +218,8 @@ class Batch:
 
     # ---- reference accessors ---------------------------------------------------------------------------------------
     def get(self, field: Data) -> Tensor:
+        if field.kind == "wide":  # two int16 columns, decoded as Datum.get does
+            return 65535 * (self.int_tensor[:, field.idx] + 32768) + (self.int_tensor[:, field.idx + 1] + 32768)
         return (self.int_tensor if field.kind == "int" else self.float_tensor)[:, field.idx]
 
     def get_training_labels(self) -> Tensor:

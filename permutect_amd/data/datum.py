@@ -24,6 +24,10 @@ class Data(enum.Enum):
     ORIGINAL_NORMAL_DEPTH = ("int", 7)
     ORIGINAL_NORMAL_ALT_COUNT = ("int", 8)
     CONTIG = ("int", 9)
+    # 32-bit values in TWO int16 columns each (reference data/datum.py:63-65)
+    POSITION = ("wide", 10)
+    REF_ALLELE_AS_BASE_5 = ("wide", 12)
+    ALT_ALLELE_AS_BASE_5 = ("wide", 14)
     # float array columns
     SEQ_ERROR_LOG_LK = ("float", 0)
     NORMAL_SEQ_ERROR_LOG_LK = ("float", 1)
@@ -35,6 +39,26 @@ class Data(enum.Enum):
     def __init__(self, kind: str, idx: int):
         self.kind = kind
         self.idx = idx
+
+
+BIGGEST_UINT16 = 65535  # reference data/datum.py:28: the MULTIPLIER of the high half of a wide field (not 65536)
+
+
+def wide_from_two_int16s(hi, lo):
+    """reference data/datum.py:46-48 `uint32_from_two_int16s`, on Python ints or integer arrays (int64 arithmetic)"""
+    if isinstance(hi, np.ndarray):
+        return BIGGEST_UINT16 * (hi.astype(np.int64) + 32768) + (lo.astype(np.int64) + 32768)
+    return BIGGEST_UINT16 * (int(hi) + 32768) + (int(lo) + 32768)
+
+
+def bases5_as_base_string(base5: int) -> str:
+    """reference utils/allele_utils.py:77-85: base-5 digits, least significant first, 1 = A, 2 = C, 3 = G, anything else = T"""
+    result, remaining = "", int(base5)
+    while remaining > 0:
+        digit = remaining % 5
+        result += "A" if digit == 1 else ("C" if digit == 2 else ("G" if digit == 3 else "T"))
+        remaining = (remaining - digit) // 5
+    return result
 
 
 NUM_SCALAR_INT_ELEMENTS = 16
@@ -56,9 +80,20 @@ class Datum:
         assert reads_re.dtype == (np.uint8 if compressed else np.float16)
 
     def get(self, field: Data):
+        if field.kind == "wide":
+            return wide_from_two_int16s(self.int_array[field.idx], self.int_array[field.idx + 1])
         return (self.int_array if field.kind == "int" else self.float_array)[field.idx]
 
+    def get_ref_allele(self) -> str:
+        return bases5_as_base_string(self.get(Data.REF_ALLELE_AS_BASE_5))
+
+    def get_alt_allele(self) -> str:
+        return bases5_as_base_string(self.get(Data.ALT_ALLELE_AS_BASE_5))
+
     def set(self, field: Data, value):
+        if field.kind == "wide":  # reference data/datum.py:41-43 `uint32_to_two_int16s`
+            self.int_array[field.idx], self.int_array[field.idx + 1] = int(value) // BIGGEST_UINT16 - 32768, int(value) % BIGGEST_UINT16 - 32768
+            return
         (self.int_array if field.kind == "int" else self.float_array)[field.idx] = value
 
     def get_int_array(self):

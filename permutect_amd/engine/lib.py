@@ -219,6 +219,14 @@ class PmtPruneStats(C.Structure):
                 ("reserved", i32)]
 
 
+class PmtWorstArgs(C.Structure):
+    _fields_ = [("num_variants", i32), ("queue_size", i32), ("num_alt_keys", i32), ("int_elem_bytes", i32),
+                ("labels", PmtIntColumn), ("alt_counts", PmtIntColumn), ("int_rows", vp), ("int_row_stride", i64), ("logits_b", vp),
+                ("scratch_bytes", i64)]
+
+
+WORST_MAX_QUEUE, WORST_HEADER_WORDS = 1024, 16  # PMT_WORST_MAX_QUEUE, PMT_WORST_HEADER_WORDS
+
 PRUNE_NO_ARTIFACT, PRUNE_NO_NONARTIFACT, PRUNE_CONFUSION_COLUMN, PRUNE_RATES_SUM_TO_ONE, PRUNE_LEVEL_RANGE = 1, 2, 4, 8, 16
 
 EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", "pmt_model_shape", "pmt_limits", "pmt_struct_bytes", "pmt_model_check", "pmt_plan_groups", "pmt_plan_groups_device", "pmt_plan_device_chunks", "pmt_stash_bytes", "pmt_pack_params",
@@ -227,7 +235,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -300,6 +308,12 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_prune_scratch_bytes.restype = C.c_size_t
     lib.pmt_prune_thresholds.argtypes = [P(PmtPruneArgs), vp, vp, vp]
     lib.pmt_prune_select.argtypes = [P(PmtPruneArgs), C.c_float, C.c_float, vp, vp, vp, vp]
+    lib.pmt_worst_table_bytes.argtypes = [i32, i32]
+    lib.pmt_worst_table_bytes.restype = C.c_size_t
+    lib.pmt_worst_scratch_bytes.argtypes = [i64, i32, i32]
+    lib.pmt_worst_scratch_bytes.restype = C.c_size_t
+    lib.pmt_worst_record.argtypes = [P(PmtWorstArgs), vp, vp, vp]
+    lib.pmt_worst_merge.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.pmt_plan_groups_split.argtypes = [vp, vp, i32, vp, vp, i32, P(i32)]
     lib.pmt_layered_scratch_floats.argtypes = [P(PmtModel), i64, i32]
     lib.pmt_layered_scratch_floats.restype = C.c_size_t
@@ -335,14 +349,15 @@ def load(path: str = None) -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("pmt_abi_version", "pmt_stash_bytes", "pmt_rows_stash_bytes", "pmt_layered_scratch_floats",
                         "pmt_layered_backward_scratch_floats", "pmt_cnn_stash_floats", "pmt_cnn_workspace_floats",
-                        "pmt_rows_workspace_floats", "pmt_cnn_bn_workspace_floats", "pmt_prune_scratch_bytes"):
+                        "pmt_rows_workspace_floats", "pmt_cnn_bn_workspace_floats", "pmt_prune_scratch_bytes", "pmt_worst_table_bytes",
+                        "pmt_worst_scratch_bytes"):
             fn.restype = i32
     lib.pmt_struct_bytes.argtypes = [i32]
     if lib.pmt_abi_version() != ABI_VERSION:
         raise PmtError("libpermutect_amd.so ABI version mismatch; rebuild it")
     for which, st in enumerate([PmtModel, PmtBatch, PmtOutputs, PmtOutputGrads, PmtAdamW, PmtLinear, PmtOp, PmtMlp,
                                 PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs,
-                                PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats]):
+                                PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs]):
         if lib.pmt_struct_bytes(which) != C.sizeof(st):
             raise PmtError(f"ctypes layout of {st.__name__} ({C.sizeof(st)} B) does not match the library "
                            f"({lib.pmt_struct_bytes(which)} B)")

@@ -23,6 +23,7 @@ from permutect_amd.training.distributed import init_from_env
 from permutect_amd.training.model_training import train_artifact_model
 
 NUM_FOLDS = 10  # reference :33
+WORST_OFFENDERS_OUTPUT_NAME = "worst_offenders_output"
 
 
 def main_without_parsing(args, log=print):
@@ -55,11 +56,17 @@ def main_without_parsing(args, log=print):
                               num_info_features=train_dataset.num_info_features(), haplotypes_length=train_dataset.haplotypes_length(),
                               device=device)
     stage("model load" if pretrained is not None else "model build")
-    history = train_artifact_model(model, train_dataset, valid_dataset, training_params, dist=dist, log=log, timing_log=log)
+    worst_path = getattr(args, WORST_OFFENDERS_OUTPUT_NAME, None)
+    worst = [] if worst_path else None
+    history = train_artifact_model(model, train_dataset, valid_dataset, training_params, dist=dist, log=log, timing_log=log,
+                                   worst_offenders=worst)
     stage("training (downsampler fit + epochs, each with a line of its own above)")
     if rank == 0:
         model.save_model(path=getattr(args, constants.OUTPUT_NAME))
         stage("save")
+        if worst:  # the last evaluation pass's table, already joined over the ranks (reference model_training.py:294-303)
+            worst[0].write_tsv(worst_path)
+            stage("worst offenders report")
     if dist is not None:
         dist.barrier()  # (nobody leaves -- and tears the process group down -- while rank 0 still writes)
     return history
@@ -72,6 +79,9 @@ def parse_arguments(argv=None):
     parser.add_argument("--" + constants.TRAIN_TAR_NAME, type=str, required=True, help="dataset tar produced by the reference's preprocess_dataset")
     parser.add_argument("--" + constants.OUTPUT_NAME, type=str, required=True, help="output artifact model file (.pt, the reference's format)")
     parser.add_argument("--" + constants.TENSORBOARD_DIR_NAME, type=str, default="tensorboard", required=False, help="accepted and ignored")
+    parser.add_argument("--" + WORST_OFFENDERS_OUTPUT_NAME, type=str, default=None, required=False,
+                        help="TSV of the worst offenders of the last evaluation pass: per (label, alt-count bin) the labeled variants the "
+                             "model contradicts most confidently")
     return parser.parse_args(argv)
 
 

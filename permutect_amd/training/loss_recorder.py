@@ -190,14 +190,22 @@ class EvaluationCounts:
 
 @torch.inference_mode()
 def collect_evaluation_data(model, balancer, downsampler, train_loader, valid_loader, seed: int = 0,
-                            fix_alt_gather: bool = False, passes: int = 3) -> EvaluationCounts:
+                            fix_alt_gather: bool = False, passes: int = 3, report_worst: bool = False,
+                            worst_queue_size: int = 100) -> EvaluationCounts:
     """The evaluation pass as the reference runs it after every validation epoch (training/model_training.py:204-228):
     over the training AND the validation loader, every parent batch downsampled `passes` = 3 times (fresh fractions each
     time), forward with the balancer's weights, results recorded.  Here each downsampling is two launches and each forward
-    the fused filter kernel; nothing returns to the host inside the loop."""
+    the fused filter kernel; nothing returns to the host inside the loop.
+    `report_worst` (reference :232-268): every recorded step also goes into a table of the worst offenders on the device (one
+    pmt_worst_record call, training/worst_offenders.py), `worst_queue_size` per (label, alt-count bin); it hangs on the returned object
+    as `worst_offenders` (None when off)."""
     was_training = model.training
     model.train(False)
     ev = EvaluationCounts(model._device, num_sources=getattr(balancer, "num_sources", None) or getattr(downsampler, "num_sources", 1))
+    ev.worst_offenders = None
+    if report_worst:
+        from permutect_amd.training.worst_offenders import WorstOffenders
+        ev.worst_offenders = WorstOffenders(model._device, queue_size=worst_queue_size)
     step = seed * 7_368_787
     for epoch_index, loader in enumerate((train_loader, valid_loader)):
         if loader is None:
@@ -208,5 +216,7 @@ def collect_evaluation_data(model, balancer, downsampler, train_loader, valid_lo
                 batch = downsampler.downsample(parent, seed=step, fix_alt_gather=fix_alt_gather)
                 out = model.compute_batch_output(batch, balancer)
                 ev.record_batch(epoch_index, batch, out.logits_b, out.weights)
+                if report_worst:
+                    ev.worst_offenders.record_batch(batch, out.logits_b)
     model.train(was_training)
     return ev

@@ -6,7 +6,7 @@ bookkeeping per (source, label, variant type, count bins), ReduceLROnPlateau on 
 keep/rollback, a validation pass per epoch.  What differs is where the work happens: batches are composed on the device
 from HBM-resident chunks, downsampling is two launches, forward / losses / backward / clip + AdamW are the fused kernels,
 and the only host synchronisations are one per epoch (mean loss for the scheduler and the checkpoint decision).  Plots,
-tensorboard and the worst-offender report of the reference are out of scope."""
+tensorboard of the reference are out of scope; its worst-offender report is training/worst_offenders.py."""
 from __future__ import annotations
 
 import math
@@ -98,13 +98,16 @@ def training_params_fit_downsampler(training_params) -> bool:
 def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Optional[ReadsDataset],
                          training_params: TrainingParameters, chunk_variants: Optional[int] = 1 << 18, seed: int = 0,
                          dist=None, log=print, fix_alt_gather: bool = False, evaluate_every_epoch: bool = True,
-                         evaluations: Optional[list] = None, timing_log=None):
+                         evaluations: Optional[list] = None, timing_log=None, worst_offenders: Optional[list] = None,
+                         worst_queue_size: int = 100):
     """`timing_log`: where the wall-time lines go (`downsampler fit: ...`, `epochs: ...`); None (the default): nowhere, so that callers
     that do not ask for them see what they saw before.  They do not go through `log`, whose lines are one per epoch half, evaluation
     pass and rollback and are counted as such (tests/test_dataset_gpu.py); the training CLI passes its `log` for both.
     `fix_alt_gather`: the reference's DownsampledBatch gathers the kept alt reads without the offset of the ref region
     (SURVEY 0.5b), so its training steps see ref rows in place of alt reads; False reproduces that, True gathers the
-    intended rows."""
+    intended rows.
+    `worst_offenders`: a list that receives the WorstOffenders table (training/worst_offenders.py) of the LAST evaluation pass, joined
+    over the ranks; None (the default): no such table is kept."""
     device = model._device
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist is not None else (0, 1)
     # datasets that fit host memory are page-locked once: their chunks then go to HBM by DMA straight from the dataset (a dataset
@@ -213,9 +216,14 @@ def train_artifact_model(model, train_dataset: ReadsDataset, valid_dataset: Opti
                                                 rank=rank, world_size=world),
                     valid_dataset.device_loader(training_params.inference_batch_size, device, chunk_variants=chunk_variants, shuffle=False,
                                                 rank=rank, world_size=world),
-                    seed=seed * 1000 + epoch, fix_alt_gather=fix_alt_gather)
+                    seed=seed * 1000 + epoch, fix_alt_gather=fix_alt_gather,
+                    report_worst=worst_offenders is not None and epoch == last_epoch, worst_queue_size=worst_queue_size)
                 if dist is not None:
                     ev.all_reduce(dist)  # every tally (histogram, call counts, logit sums) in one collective
+                    if ev.worst_offenders is not None:
+                        ev.worst_offenders.all_reduce(dist)  # one gather of the fixed-size tables
+                if ev.worst_offenders is not None:
+                    worst_offenders[:] = [ev.worst_offenders]
                 model.engine().check_join_fault()
                 log(f"epoch {epoch} evaluation: accuracy train {ev.accuracy(0):.4f}, valid {ev.accuracy(1):.4f}")
                 evaluations.append((epoch, ev.accuracy(0), ev.accuracy(1)))
