@@ -331,7 +331,7 @@ int pmt_build_id(char* out, int32_t capacity);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * 0 PmtModel, 1 PmtBatch, 2 PmtOutputs, 3 PmtOutputGrads, 4 PmtAdamW, 5 PmtLinear, 6 PmtOp, 7 PmtMlp, 8 PmtBlock, 9 PmtHead,
  * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs, 16 PmtPosteriorRows,
- * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs */
+ * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs, 21 PmtPosteriorEvalArgs */
 int pmt_struct_bytes(int which);
 
 /* Validates a descriptor against the kernels' limits. */
@@ -505,6 +505,68 @@ int pmt_posterior_update(const float* partials, int32_t num_partial_rows, int64_
 #define PMT_CONTEXT_FIXED_ONE (1ll << 30)
 int pmt_posterior_step_context(const PmtPosteriorRows* rows, int64_t first, int64_t count, const PmtPosteriorParams* params, float* partials,
                                int32_t num_partial_rows, unsigned long long* somatic_snv_fixed_rrra, void* stream);
+
+/* A filtering run scored against truth labels (reference tools/filter_variants.py:381-411, :534-588: `EvaluationMetrics.record_batch(...,
+ * use_original_counts=True)` of the error logit, `AccuracyMetrics.record_with_sources_and_logits` of the cached artifact logit by
+ * most-confident call, the correctness decision tree and the mistakes): one pass over rows [first, first + count), a lane per candidate,
+ * the posterior of pmt_posterior_forward in double (csrc/pmt_posterior_device.hpp: po_row), everything tallied into INTEGER tables.
+ *   labels [n], filtered_in [n] (may be NULL): columns beside `rows`, read at first + i.  The per-row outputs [count] (each may be NULL)
+ *   are written at i = 0 .. count - 1, like pmt_posterior_forward's.
+ * Per row, p_c = softmax of the five log posteriors in double:
+ *   error_prob = 1 - p[passing_call], written as float; error_logit = log(c / (1 - c)) with c = 0.5 + 0.9999999 (error_prob - 0.5)
+ *   (reference utils/math_utils.py:26-28), evaluated in double, written as float; a logit x falls into bin
+ *   floor(min(max(x, -10), 10) + 10) of 21 (reference data/count_binning.py:14-45) -- x being the FLOAT that is written;
+ *   most_confident_call = argmax_c p_c (the lowest index among equals), most_confident_prob = that p as float;
+ *   filtered = filtered_in[first + i] != 0 where given, else error_prob (the float) > thresholds_v[type], strictly (reference :535-537);
+ *   error_call = for a filtered row argmax over c != passing_call (lowest index among equals; reference :541-548), else -1;
+ *   correctness (reference :559-589): 0 unknown (unlabeled rows, and what the reference leaves "unknown"), 1 true-positive,
+ *   2 true-negative-artifact, 3 false-negative-artifact, 4 false-positive;
+ *   count bins from the ORIGINAL counts (reference data/batch.py:72-77): ref bin = min(max(depth - alt, 0), 10) / 3, alt bin =
+ *   (min(max(alt, 1), 15) - 1) / 3.  The reference's floor division gives bin -1 for alt = 0 and for depth < alt (an index in front
+ *   of its table); here both are CLAMPED into bin 0.  The variant type is clamped into 0 .. 4 like everywhere else.
+ *   A row is INVALID when one of its five log posteriors or of their softmax is NaN, its cached artifact logit is NaN or its label is outside 0 .. 2
+ *   (enums.Label: 0 artifact, 1 variant, 2 unlabeled): it adds 1 to `invalid`, is tallied nowhere else, and its per-row outputs are
+ *   NaN (floats), -1 (ints) and 0 (filtered_out_b).
+ * tables [PMT_EVAL_TABLE_WORDS] of 64-bit words, ADDED into (the caller zeroes them once and may call in slices):
+ *   PMT_EVAL_TRUTH_HIST  [3 L][5 V][4 R][5 A][21 G]     labeled rows (label != 2) by label, type, ref bin, alt bin, ERROR-logit bin: 1 each
+ *   PMT_EVAL_CALL_HIST   [5 C][3 L][5 V][4 R][5 A][21 G] every valid row by most-confident call, ..., bin of its CACHED ARTIFACT logit:
+ *                        llrint(most_confident_prob (the float) * 2^30) each (PMT_CONTEXT_FIXED_ONE, as pmt_posterior_step_context)
+ *   PMT_EVAL_CONFUSION   [5 V][3 L][2]                   every valid row by type, label, filtered
+ *   PMT_EVAL_MISTAKES    [5 C][5 V]                      labeled rows called wrongly (filtered with label variant, passed with label
+ *                        artifact) under their bad call: error_call if filtered, else passing_call (the reference writes Call.SOMATIC
+ *                        there in germline mode too, under a TODO; in somatic mode the two agree)
+ *   PMT_EVAL_INVALID     [1]
+ * Every add is an integer add, so the tables' bits depend neither on the grid nor on slicing, arrival order or the run.  Persistent
+ * workgroups walk the rows grid-stride; the small tables are counted in a private LDS copy and added once per workgroup, call_hist's
+ * equal keys are summed within a wavefront before one 64-bit vector atomic.  num_workgroups: 0 = the library's choice.
+ * A NULL struct, column, labels, thresholds_v, tables or parameter array, passing_call other than 0 or 3, num_workgroups < 0, first < 0,
+ * count < 0 or first + count > n: PMT_E_INVALID, nothing launched.  count == 0: PMT_OK, nothing written. */
+#define PMT_EVAL_LABELS 3
+#define PMT_EVAL_REF_BINS 4
+#define PMT_EVAL_ALT_BINS 5
+#define PMT_EVAL_LOGIT_BINS 21
+#define PMT_EVAL_CELLS (PMT_EVAL_LABELS * 5 * PMT_EVAL_REF_BINS * PMT_EVAL_ALT_BINS * PMT_EVAL_LOGIT_BINS) /* 6300 */
+#define PMT_EVAL_TRUTH_HIST 0
+#define PMT_EVAL_CALL_HIST (PMT_EVAL_TRUTH_HIST + PMT_EVAL_CELLS)
+#define PMT_EVAL_CONFUSION (PMT_EVAL_CALL_HIST + 5 * PMT_EVAL_CELLS)
+#define PMT_EVAL_MISTAKES (PMT_EVAL_CONFUSION + 5 * PMT_EVAL_LABELS * 2)
+#define PMT_EVAL_INVALID (PMT_EVAL_MISTAKES + 5 * 5)
+#define PMT_EVAL_TABLE_WORDS (PMT_EVAL_INVALID + 1) /* 37856 */
+typedef struct PmtPosteriorEvalArgs {
+    const int32_t* labels;
+    const float* thresholds_v; /* [5] error-probability threshold per variant type */
+    const uint8_t* filtered_in;
+    float *error_probs_b, *error_logits_b;
+    int32_t* most_confident_call_b;
+    float* most_confident_prob_b;
+    uint8_t* filtered_out_b;
+    int32_t *error_call_b, *correctness_b;
+    unsigned long long* tables;
+    int32_t passing_call; /* 0 somatic, 3 germline (germline mode) */
+    int32_t num_workgroups;
+} PmtPosteriorEvalArgs;
+int pmt_posterior_evaluate(const PmtPosteriorRows* rows, int64_t first, int64_t count, const PmtPosteriorParams* params,
+                           const PmtPosteriorEvalArgs* args, void* stream);
 
 /* The M step of the context-dependent SNV priors (reference posterior_model_priors.py:158-222) as ONE persistent launch of one
  * wavefront.  The reference fits its generative model of per-context mutation rates by pymc's mean-field ADVI and reports the mean of

@@ -43,6 +43,7 @@ extern "C" int pmt_struct_bytes(int which) {
         case 18: return (int)sizeof(PmtPruneArgs);
         case 19: return (int)sizeof(PmtPruneStats);
         case 20: return (int)sizeof(PmtWorstArgs);
+        case 21: return (int)sizeof(PmtPosteriorEvalArgs);
         default: return PMT_E_INVALID;
     }
 }

@@ -207,6 +207,19 @@ class PmtPosteriorParams(C.Structure):
                 ("has_het_beta", i32), ("het_beta", C.c_float)]
 
 
+class PmtPosteriorEvalArgs(C.Structure):
+    _fields_ = [("labels", vp), ("thresholds_v", vp), ("filtered_in", vp), ("error_probs_b", vp), ("error_logits_b", vp),
+                ("most_confident_call_b", vp), ("most_confident_prob_b", vp), ("filtered_out_b", vp), ("error_call_b", vp),
+                ("correctness_b", vp), ("tables", vp), ("passing_call", i32), ("num_workgroups", i32)]
+
+
+# the flat table of pmt_posterior_evaluate in 64-bit words (PMT_EVAL_*): truth_hist [3][5][4][5][21], call_hist [5][3][5][4][5][21],
+# confusion [5][3][2], mistakes [5][5], invalid [1]
+EVAL_CELLS = 3 * 5 * 4 * 5 * 21
+EVAL_TRUTH_HIST, EVAL_CALL_HIST, EVAL_CONFUSION = 0, EVAL_CELLS, 6 * EVAL_CELLS
+EVAL_MISTAKES, EVAL_INVALID, EVAL_TABLE_WORDS = EVAL_CONFUSION + 30, EVAL_CONFUSION + 55, EVAL_CONFUSION + 56
+
+
 class PmtPruneArgs(C.Structure):
     _fields_ = [("n", i64), ("art_probs", vp), ("labels", PmtIntColumn), ("label_art_frac", C.c_double), ("levels", C.c_double * 2),
                 ("levels_given", i32), ("reserved", i32)]
@@ -235,7 +248,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -336,6 +349,7 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_posterior_forward.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, vp, vp, vp, vp]
     lib.pmt_posterior_step.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, i32, vp]
     lib.pmt_posterior_step_context.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), vp, i32, vp, vp]
+    lib.pmt_posterior_evaluate.argtypes = [P(PmtPosteriorRows), i64, i64, P(PmtPosteriorParams), P(PmtPosteriorEvalArgs), vp]
     lib.pmt_context_priors_fit.argtypes = [vp, vp, vp, C.c_double, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     lib.pmt_posterior_update.argtypes = [vp, i32, i64, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     lib.pmt_balance_step.argtypes = [P(PmtBalanceArgs), vp]
@@ -357,7 +371,7 @@ def load(path: str = None) -> C.CDLL:
         raise PmtError("libpermutect_amd.so ABI version mismatch; rebuild it")
     for which, st in enumerate([PmtModel, PmtBatch, PmtOutputs, PmtOutputGrads, PmtAdamW, PmtLinear, PmtOp, PmtMlp,
                                 PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs,
-                                PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs]):
+                                PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs, PmtPosteriorEvalArgs]):
         if lib.pmt_struct_bytes(which) != C.sizeof(st):
             raise PmtError(f"ctypes layout of {st.__name__} ({C.sizeof(st)} B) does not match the library "
                            f"({lib.pmt_struct_bytes(which)} B)")

@@ -19,7 +19,14 @@ rates, one persistent launch on the device -- NOT the reference's stochastic pym
 (tools/filter_variants.py:242, :265), not used.
 
     ... --genomic_span 3e9 --calls_output calls.npz [--num_spectrum_iterations 10] [--germline_mode | --no_germline_mode] [--het_beta B]
-        [--context_dependent_snv_priors]
+        [--context_dependent_snv_priors] [--evaluation_output eval.npz]
+
+With `--evaluation_output` and candidates that carry truth labels (reference tools/filter_variants.py:381-411, :534-617) rank 0 then scores
+the calls it has just written: one pass over the rows on the device (architecture/posterior_evaluation.py: pmt_posterior_evaluate)
+tallies the error logit by label, the cached artifact logit by most-confident call, the filter's confusion counts and the mistakes into
+integer tables; the .npz holds the tables, the sensitivity / precision curve of every variant type over all counts
+(metrics/accuracy_curves.py), the thresholds as logits, sensitivity and precision at those thresholds, and the row indices and bad calls
+of the mistakes.  The filter decisions are the `filtered_b` of --calls_output, passed on.  The reference's plots are not drawn.
 
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N -m permutect_amd.tools.filter_variants ...`: WORLD_SIZE > 1) the
 candidates are cut into N contiguous shards, one process per GPU, no collective on the data path; rank 0 concatenates the shards'
@@ -114,7 +121,31 @@ def run_posterior_stage(args, posterior: MemoryMappedData, device, log=print):
     if context and model.priors.last_context_fit is not None:
         log(f"context-dependent SNV priors: the last fit's largest |dF / d unknown| / max(sum k, 1) = {model.priors.last_context_fit_max_grad():.3e} "
             "(a deterministic estimator of the reference's model, not its ADVI fit)")
+    if getattr(args, "evaluation_output", None):
+        run_evaluation(args, posterior, rows, model, thresholds, out["filtered_b"], germline_mode, log)
     return model, out
+
+
+def run_evaluation(args, posterior: MemoryMappedData, rows, model, thresholds, filtered_b, germline_mode: bool, log=print):
+    """--evaluation_output: the calls against the truth labels of the candidates (architecture/posterior_evaluation.py)"""
+    from permutect_amd.architecture.posterior_evaluation import evaluate_against_truth, posterior_labels
+    from permutect_amd.enums import Label, Variation
+    t0 = time.perf_counter()
+    labels_b = posterior_labels(posterior, device=rows.device)
+    evaluation = evaluate_against_truth(model, rows, labels_b, thresholds, germline_mode=germline_mode,
+                                        filtered_b=torch.from_numpy(filtered_b), keep_rows=True)
+    evaluation.save(getattr(args, "evaluation_output"))
+    labeled = evaluation.num_labeled()
+    log(f"evaluation against truth: {labeled} labeled of {len(rows)} candidates, {evaluation.invalid} invalid, "
+        f"{int(evaluation.mistakes.sum())} mistakes in {time.perf_counter() - t0:.3f} s"
+        + ("" if labeled else "; no labeled candidates: the tables are empty"))
+    sensitivity_v, precision_v = evaluation.sensitivity_precision()
+    for v in Variation:
+        c = evaluation.confusion[v]
+        log(f"  {v.name}: variants {int(c[Label.VARIANT, 0])} passed / {int(c[Label.VARIANT, 1])} filtered, artifacts "
+            f"{int(c[Label.ARTIFACT, 0])} passed / {int(c[Label.ARTIFACT, 1])} filtered, sensitivity {float(sensitivity_v[v]):.4f}, "
+            f"precision {float(precision_v[v]):.4f} at threshold logit {float(evaluation.threshold_logits()[v]):.3f}")
+    return evaluation
 
 
 def parse_arguments(argv=None):
@@ -138,10 +169,14 @@ def parse_arguments(argv=None):
     parser.add_argument("--context_dependent_snv_priors", action="store_true",
                         help="learn the SNV prior per 3-base context and substitution in the second half of the epochs (a deterministic "
                              "estimator of the reference's model, not its ADVI fit)")
+    parser.add_argument("--evaluation_output", type=str, default=None, required=False,
+                        help="output .npz of the calls scored against the candidates' truth labels (with --genomic_span)")
     parser.add_argument("--recall_weight", type=float, default=1.0, required=False, help="weight of recall against precision in the F-beta score")
     args = parser.parse_args(argv)
     if posterior_stage_requested(args) and not args.calls_output:
         parser.error("--genomic_span runs the posterior stage, which needs --calls_output")
+    if args.evaluation_output and not posterior_stage_requested(args):
+        parser.error("--evaluation_output scores the posterior stage's calls, which needs --genomic_span")
     return args
 
 
