@@ -331,7 +331,7 @@ int pmt_build_id(char* out, int32_t capacity);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * 0 PmtModel, 1 PmtBatch, 2 PmtOutputs, 3 PmtOutputGrads, 4 PmtAdamW, 5 PmtLinear, 6 PmtOp, 7 PmtMlp, 8 PmtBlock, 9 PmtHead,
  * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs, 16 PmtPosteriorRows,
- * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs, 21 PmtPosteriorEvalArgs */
+ * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs, 21 PmtPosteriorEvalArgs, 22 PmtAnnotateArgs */
 int pmt_struct_bytes(int which);
 
 /* Validates a descriptor against the kernels' limits. */
@@ -759,6 +759,54 @@ int pmt_worst_record(const PmtWorstArgs* args, void* table, void* scratch, void*
  * header's counts added and its largest alt count the larger.  `other` is only read and must not be `table` (PMT_E_INVALID); `scratch`
  * is not used and may be NULL. */
 int pmt_worst_merge(void* table, const void* other, int32_t queue_size, int32_t num_alt_keys, void* scratch, void* stream);
+
+/* The site annotation of filter_variants (reference data/memory_mapped_data.py:131-175 `generate_vcf_annotated_data`, fed by
+ * tools/filter_variants.py:167-182 `get_segmentation` and misc_utils.py `encode`): every candidate gets its population allele frequency
+ * from the input VCF and its tumor / normal minor-allele fraction from two segmentations, and is dropped when the VCF has no record of
+ * it or Mutect2 gave it a trusted filter.  The reference keeps a dict of strings per VCF record and two IntervalTrees and builds a Datum
+ * per candidate; here the host sorts three tables once and ONE launch, a lane per candidate, looks every candidate up in all three.
+ *   A candidate's identity is columns 9 .. 15 of its int row (as PmtWorstArgs; first_column .. first_column + 6 of what is passed): contig = column 9, position / ref code / alt code =
+ *   65535 * (hi + 32768) + (lo + 32768) in 32 bits.  Its LOCUS is (contig & 0xFFFFFFFF) << 32 | position.  Its ALLELE KEY reproduces
+ *   `truncate(trim(ref, alt).alt)` of the decoded strings: base-5 digits peeled off each code least significant first while the code is
+ *   non-zero (a digit other than 1, 2, 3 counts as 4: bases5_as_base_string), trimmed from the top while both lengths exceed 1 and the
+ *   top digits agree, the lowest 13 alt digits re-encoded (A=1 C=2 G=3 T=4, first base least significant) -- below 5^13; an empty alt
+ *   gives 0, which no site has.
+ *   The site table: n_sites rows sorted ascending by (site_locus, site_alt), keys distinct.  Found: keep = !site_excluded,
+ *   allele_frequency = site_af.  Not found: keep = 0, allele_frequency = 0.
+ *   A segment table: n rows sorted ascending by start key ((contig & 0xFFFFFFFF) << 32 | start), non-overlapping; stop is the plain
+ *   coordinate; a segment covers start <= position < stop.  The answer is the maf of the last segment whose start key is at or before
+ *   the candidate's locus when that segment's contig is the candidate's and position < stop, else 0.5.
+ * Every element of the four outputs is written.  counters (six uint64, ADDED to: the caller zeroes them): kept, excluded (found with
+ * the excluded flag), unmatched, unknown contig (never touched by the kernel: the host's check owns its meaning), maf hits, normal-maf
+ * hits -- integer atomics, one per non-zero counter per workgroup, so all outputs are bit-identical for any grid and from run to run. */
+typedef struct PmtAnnotateArgs {
+    int64_t num_candidates;                    /* up to 2^31 - 1 */
+    const void* int_rows;                      /* element (i, c) at int_rows + (i * int_row_stride + c) elements */
+    int64_t int_row_stride;
+    int32_t int_elem_bytes, first_column;      /* 2, 4 or 8; where CONTIG stands in a row: 9 for whole int rows, 0 for columns 9 .. 15 alone */
+    int32_t threads_hint, reserved;            /* workgroup size 64 / 128 / 256 / 512 / 1024, 0 = 256 */
+    int64_t n_sites;
+    const uint64_t* site_locus;                /* [n_sites] */
+    const uint32_t* site_alt;
+    const float* site_af;
+    const uint8_t* site_excluded;
+    int64_t n_segments, n_normal_segments;
+    const uint64_t* seg_start;                 /* [n_segments] */
+    const uint64_t* seg_stop;
+    const float* seg_maf;
+    const uint64_t* normal_seg_start;          /* [n_normal_segments] */
+    const uint64_t* normal_seg_stop;
+    const float* normal_seg_maf;
+    float* allele_frequencies;                 /* [num_candidates] out */
+    float* mafs;
+    float* normal_mafs;
+    uint8_t* keep;
+    uint64_t* counters;                        /* [6] added to */
+} PmtAnnotateArgs;
+/* One ordinary launch on `stream`; no allocation, no synchronisation, no host read-back.  num_candidates == 0: PMT_OK, nothing launched
+ * (no output, counter or row pointer is looked at).  A NULL struct, output, counters or int_rows, num_candidates < 0 or beyond 2^31 - 1, a table size < 0 or beyond 2^31 - 1, a NULL array of a
+ * non-empty table, an element width other than 2 / 4 / 8, first_column < 0 or a row shorter than first_column + 7, or a threads_hint not listed: PMT_E_INVALID, nothing launched. */
+int pmt_annotate_sites(const PmtAnnotateArgs* args, void* stream);
 
 /* The tallies of an evaluation step (reference metrics/evaluation_metrics.py:49-66 -> AccuracyMetrics, metrics/loss_metrics.py:226-243;
  * training/model_training.py:204-228 runs it three times per parent batch after every validation epoch): the weights of the LABELED

@@ -44,6 +44,7 @@ extern "C" int pmt_struct_bytes(int which) {
         case 19: return (int)sizeof(PmtPruneStats);
         case 20: return (int)sizeof(PmtWorstArgs);
         case 21: return (int)sizeof(PmtPosteriorEvalArgs);
+        case 22: return (int)sizeof(PmtAnnotateArgs);
         default: return PMT_E_INVALID;
     }
 }

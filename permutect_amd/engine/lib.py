@@ -238,6 +238,14 @@ class PmtWorstArgs(C.Structure):
                 ("scratch_bytes", i64)]
 
 
+class PmtAnnotateArgs(C.Structure):
+    _fields_ = [("num_candidates", i64), ("int_rows", vp), ("int_row_stride", i64), ("int_elem_bytes", i32), ("first_column", i32),
+                ("threads_hint", i32), ("reserved", i32), ("n_sites", i64), ("site_locus", vp), ("site_alt", vp), ("site_af", vp),
+                ("site_excluded", vp), ("n_segments", i64), ("n_normal_segments", i64), ("seg_start", vp), ("seg_stop", vp), ("seg_maf", vp),
+                ("normal_seg_start", vp), ("normal_seg_stop", vp), ("normal_seg_maf", vp), ("allele_frequencies", vp), ("mafs", vp),
+                ("normal_mafs", vp), ("keep", vp), ("counters", vp)]
+
+
 WORST_MAX_QUEUE, WORST_HEADER_WORDS = 1024, 16  # PMT_WORST_MAX_QUEUE, PMT_WORST_HEADER_WORDS
 
 PRUNE_NO_ARTIFACT, PRUNE_NO_NONARTIFACT, PRUNE_CONFUSION_COLUMN, PRUNE_RATES_SUM_TO_ONE, PRUNE_LEVEL_RANGE = 1, 2, 4, 8, 16
@@ -248,7 +256,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_annotate_sites", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -327,6 +335,7 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_worst_scratch_bytes.restype = C.c_size_t
     lib.pmt_worst_record.argtypes = [P(PmtWorstArgs), vp, vp, vp]
     lib.pmt_worst_merge.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.pmt_annotate_sites.argtypes = [P(PmtAnnotateArgs), vp]
     lib.pmt_plan_groups_split.argtypes = [vp, vp, i32, vp, vp, i32, P(i32)]
     lib.pmt_layered_scratch_floats.argtypes = [P(PmtModel), i64, i32]
     lib.pmt_layered_scratch_floats.restype = C.c_size_t
@@ -371,7 +380,8 @@ def load(path: str = None) -> C.CDLL:
         raise PmtError("libpermutect_amd.so ABI version mismatch; rebuild it")
     for which, st in enumerate([PmtModel, PmtBatch, PmtOutputs, PmtOutputGrads, PmtAdamW, PmtLinear, PmtOp, PmtMlp,
                                 PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs,
-                                PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs, PmtPosteriorEvalArgs]):
+                                PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs, PmtPosteriorEvalArgs,
+                                PmtAnnotateArgs]):
         if lib.pmt_struct_bytes(which) != C.sizeof(st):
             raise PmtError(f"ctypes layout of {st.__name__} ({C.sizeof(st)} B) does not match the library "
                            f"({lib.pmt_struct_bytes(which)} B)")

@@ -1,11 +1,17 @@
 """The artifact-model stage of `filter_variants` on the MI355X engine (reference tools/filter_variants.py:292-320, :350-357:
 `generate_posterior_data` + `MemoryMappedData.from_generator`): every candidate of a dataset tar goes through the model's forward and
 comes out as a read-less Datum row whose info array is its embedding and whose CACHED_ARTIFACT_LOGIT is its logit -- the input of
-the posterior model.  What stands in front of this stage in the reference (plain-text parsing, VCF annotation) and the filtered VCF
-behind it are out of scope: the tool reads a dataset tar in the reference's format and writes the posterior data as a tar
-in the same format.
+the posterior model.  What stands in front of this stage in the reference (plain-text parsing) and the filtered VCF behind it are out
+of scope: the tool reads a dataset tar in the reference's format and writes the posterior data as a tar in the same format.
 
     python -m permutect_amd.tools.filter_variants --test_dataset_tar candidates.tar --artifact_model model.pt --output posterior.tar
+
+With `--input VCF --contigs_table T [--maf_segments F] [--normal_maf_segments F]` the candidates are annotated first (reference
+data/memory_mapped_data.py:131-175 behind `make_posterior_data_loader`; data/site_annotation.py here): a freshly preprocessed tar
+carries NaN in ALLELE_FREQUENCY, MAF and NORMAL_MAF; the allele frequency comes from the VCF's POPAF, the two minor-allele fractions
+from the segment files (0.5 outside every segment), and candidates that the VCF does not hold or that Mutect2 filtered as
+`contamination` or `slippage` are dropped -- one launch over the candidates' identity columns (pmt_annotate_sites).  Every rank reads
+the same files and gets the same kept list: no collective.  Without `--input` the three columns are taken as the tar has them.
 
 With `--genomic_span` the posterior stage follows (reference tools/filter_variants.py:244-289; architecture/posterior_model.py): rank 0
 turns the posterior data into device-resident columns, learns the priors and allele-fraction spectra
@@ -48,6 +54,9 @@ from permutect_amd.training.distributed import init_from_env
 TEST_DATASET_TAR_NAME = "test_dataset_tar"
 ARTIFACT_MODEL_NAME = "artifact_model"  # (reference constants.py: ARTIFACT_MODEL_NAME)
 GENOMIC_SPAN_NAME = "genomic_span"       # (reference constants.py: GENOMIC_SPAN_NAME)
+CONTIGS_TABLE_NAME = "contigs_table"             # (reference constants.py: CONTIGS_TABLE_NAME)
+MAF_SEGMENTS_NAME = "maf_segments"               # (reference constants.py: MAF_SEGMENTS_NAME)
+NORMAL_MAF_SEGMENTS_NAME = "normal_maf_segments"  # (reference constants.py: NORMAL_MAF_SEGMENTS_NAME)
 POSTERIOR_BATCH_SIZE = 64               # the reference's loader for the posterior model takes its --batch_size, 64 by default
 DEFAULT_BATCH_SIZE = 65536  # the reference's flag defaults to 64 (tools/filter_variants.py:81); the rows do not depend on it
 
@@ -58,6 +67,8 @@ def main_without_parsing(args, log=print):
     dist, rank, world, device = init_from_env()  # this rank's card and the process group, before anything else touches the GPU
     model, _, _ = load_model(getattr(args, ARTIFACT_MODEL_NAME), device=device)
     data = MemoryMappedData.load_from_tarfile(getattr(args, TEST_DATASET_TAR_NAME))
+    if getattr(args, constants.INPUT_NAME, None) is not None:
+        data = annotate_candidates(args, data, device, log if rank == 0 else (lambda *a, **k: None))
     dataset = ReadsDataset(data)
     t0 = time.perf_counter()
     posterior = make_posterior_mmap(dataset, model, getattr(args, constants.BATCH_SIZE_NAME), device=device,
@@ -72,6 +83,27 @@ def main_without_parsing(args, log=print):
     if dist is not None:
         dist.barrier()
     return posterior
+
+
+def annotate_candidates(args, data: MemoryMappedData, device, log=print) -> MemoryMappedData:
+    """--input: the three annotated float columns from the VCF and the segment files, the candidates outside the VCF or with a trusted
+    Mutect2 filter dropped (data/site_annotation.py)"""
+    from permutect_amd.data import site_annotation as S
+    contigs_path = getattr(args, CONTIGS_TABLE_NAME, None)
+    if contigs_path is None:
+        raise ValueError(f"--{constants.INPUT_NAME} names candidates by contig name: it needs --{CONTIGS_TABLE_NAME}")
+    t0 = time.perf_counter()
+    contigs = S.read_contig_indices(contigs_path)
+    sites = S.read_vcf_sites(getattr(args, constants.INPUT_NAME), contigs)
+    segments = S.read_segments(getattr(args, MAF_SEGMENTS_NAME, None), contigs)
+    normal_segments = S.read_segments(getattr(args, NORMAL_MAF_SEGMENTS_NAME, None), contigs)
+    t1 = time.perf_counter()
+    annotated, counts = S.annotate_dataset(data, sites, segments, normal_segments, device)
+    t2 = time.perf_counter()
+    log(f"site annotation: {len(data)} candidates against {len(sites)} sites ({sites.num_records} VCF records), {len(segments)} / "
+        f"{len(normal_segments)} segments: " + ", ".join(f"{name} {count}" for name, count in counts.items())
+        + f"; read {t1 - t0:.3f} s, annotate {t2 - t1:.3f} s")
+    return annotated
 
 
 def posterior_stage_requested(args) -> bool:
@@ -155,6 +187,14 @@ def parse_arguments(argv=None):
     parser.add_argument("--" + constants.OUTPUT_NAME, type=str, required=True, help="output tar of the posterior data")
     parser.add_argument("--" + constants.BATCH_SIZE_NAME, type=int, default=DEFAULT_BATCH_SIZE, required=False, help="batch size")
     parser.add_argument("--chunk_variants", type=int, default=None, required=False, help="candidates per HBM-resident chunk (default: the loader's)")
+    # the site annotation (the reference's names); without --input nothing of it runs
+    parser.add_argument("--" + constants.INPUT_NAME, type=str, default=None, required=False,
+                        help="the Mutect2 VCF of the candidates: POPAF and the trusted filters are read from it (needs --contigs_table)")
+    parser.add_argument("--" + CONTIGS_TABLE_NAME, type=str, default=None, required=False, help="table of `name index` lines: the dataset's contig indices")
+    parser.add_argument("--" + MAF_SEGMENTS_NAME, type=str, default=None, required=False,
+                        help="segments of the tumor's minor-allele fraction: contig, start, stop, maf (with --input)")
+    parser.add_argument("--" + NORMAL_MAF_SEGMENTS_NAME, type=str, default=None, required=False,
+                        help="segments of the normal's minor-allele fraction (with --input)")
     # the posterior stage (the reference's names and defaults, tools/filter_variants.py:83-163); without --genomic_span nothing of it runs
     parser.add_argument("--" + GENOMIC_SPAN_NAME, type=float, default=None, required=False,
                         help="number of sites considered by Mutect2, candidates or not: runs the posterior model behind the artifact model")
@@ -173,6 +213,11 @@ def parse_arguments(argv=None):
                         help="output .npz of the calls scored against the candidates' truth labels (with --genomic_span)")
     parser.add_argument("--recall_weight", type=float, default=1.0, required=False, help="weight of recall against precision in the F-beta score")
     args = parser.parse_args(argv)
+    if getattr(args, constants.INPUT_NAME) is not None and getattr(args, CONTIGS_TABLE_NAME) is None:
+        parser.error(f"--{constants.INPUT_NAME} names candidates by contig name: it needs --{CONTIGS_TABLE_NAME}")
+    for name in (MAF_SEGMENTS_NAME, NORMAL_MAF_SEGMENTS_NAME):
+        if getattr(args, name) is not None and getattr(args, constants.INPUT_NAME) is None:
+            parser.error(f"--{name} annotates the candidates of --{constants.INPUT_NAME}, which is missing")
     if posterior_stage_requested(args) and not args.calls_output:
         parser.error("--genomic_span runs the posterior stage, which needs --calls_output")
     if args.evaluation_output and not posterior_stage_requested(args):
