@@ -1,7 +1,10 @@
 // Haplotype CNN, batched-column kernels: the production-shaped stack
 //     Conv1d(10 -> C1, k1) -> MaxPool1d(2) -> act -> Conv1d(C1 -> C2, k2) -> act -> Flatten -> Linear(C2 * L2 -> O)
 // (reference architecture/dna_sequence_convolution.py:31-111 on the one-hot of data/batch.py:115-130) as plain GEMMs on the
-// fp32 matrix core (v_mfma_f32_16x16x4_f32: exact fp32, like the reference).
+// matrix core.  The fp32 forward and the backward's input-gradient chain run on v_mfma_f32_16x16x4_f32 (exact fp32, like the
+// reference); the production forward runs fp32-equivalent products on two f16 pieces per operand; the backward's convolution
+// WEIGHT gradients, leaves whose rounding goes no further, run 32-deep bf16 products on two pieces per operand (16 significant
+// bits, ~2e-6 relative L2 on the gradient; see "backward" below).
 //
 // pmt_cnn2.hip gives a wave ONE variant: a convolution's 7 or 19 output positions half-fill its 16-column tiles, every B
 // operand is an im2col gather through a tap table (~10 instructions per element) and the input gradient is a col2im of LDS
@@ -12,10 +15,12 @@
 //     16 channels, no index arithmetic, no tap table; its output registers are stored with one ds_write_b128 per 16 channels;
 //   * the input gradient is the same gather with the transposed weights (out[q] = sum_k W_k^T dY[q - k]): plain stores, no
 //     atomics;
-//   * weight gradients contract over columns, their operands read from the same LDS arrays (a scalar per lane and k-step),
-//     accumulated in registers over ALL the variants a wave sees (the kernels are persistent) and added to global memory once
-//     per wave;
-//   * the one-hot input is never materialised: a B operand of the first convolution is a byte compare on the haplotype;
+//   * weight gradients contract over columns, accumulated in registers over ALL the variants a wave sees (the kernels are
+//     persistent) and added to global memory once per wave.  The linear's reads its operands from the same LDS arrays (a
+//     scalar per lane and k-step); the convolutions' read theirs from variant-fastest "k images" of the same values, eight
+//     variants of one position per lane, and split them into two bf16 pieces in registers;
+//   * the fp32 forward never materialises the one-hot input: a B operand of its first convolution is a byte compare on the
+//     haplotype (the f16 forward and the backward keep it in LDS as 16-bit ones and zeros);
 //   * max-pooling pairs neighbouring columns of the first convolution's output with one DPP shift (its argmax goes into the
 //     stash as one bit per channel); the first convolution's weight gradient uses the pooled gradient directly, split by argmax.
 // No workgroup barrier after the prologue: a wave's LDS traffic completes in order (wave_sync).
@@ -132,10 +137,10 @@ DEV C3Weights c3_build_weights(const C3Cfg& c, const float* __restrict__ theta, 
     return W;
 }
 
-// per-wave LDS region (floats): [V records][x: V * st2 * 32 (backward scratch)][dout: V * 16][hap: V * 2 S bytes].
+// per-wave LDS region of the fp32 FORWARD (floats): [V records][x: V * st2 * 32][dout: V * 16][hap: V * 2 S bytes] (C3Cfg.per_wave;
+// x and dout are left from the time the backward shared this layout: the backward has its own region now, c3w_floats below).
 // A RECORD is what the forward leaves of one variant and the backward needs: [a1: P1 * 32][a2: st2 * 32][pool argmax: P1 words],
-// padded to a multiple of 4 floats -- in LDS exactly as in the stash, so a batch's stash moves with 16-byte copies whose
-// loads are all issued before the first store (a load / store loop exposes one HBM latency per iteration).
+// padded to a multiple of 4 floats -- in the forward's LDS exactly as in the stash, so a batch's records leave with 16-byte copies.
 #define C3_COPY_F4 20   // f4 per lane a batch copy may take: V * rec / 4 <= 64 * C3_COPY_F4
 #define C3_HAP_LOADS 8  // V * 2 S <= 64 * C3_HAP_LOADS
 struct C3Wave {
@@ -178,23 +183,7 @@ DEV void c3_load_haplotypes(const C3Cfg& c, const C3Wave& w, const long long* __
         if (i < V * n2s) w.hap[i] = (b[k] >= 0 && b[k] < 5) ? (unsigned char)b[k] : (unsigned char)255;  // anything else matches no one-hot channel
     }
 }
-// the records of a batch: stash -> LDS (zeros for variants beyond the end) / LDS -> stash
-template <int V>
-DEV void c3_load_records(const C3Wave& w, const float* __restrict__ src, int nv) {
-    const int lane = threadIdx.x & 63, have = nv * w.rec_floats / 4, all = V * w.rec_floats / 4;
-    f4 t[C3_COPY_F4];
-#pragma unroll
-    for (int k = 0; k < C3_COPY_F4; ++k) {
-        const int i = lane + 64 * k;
-        t[k] = f4{0.f, 0.f, 0.f, 0.f};
-        if (i < have) t[k] = reinterpret_cast<const f4*>(src)[i];
-    }
-#pragma unroll
-    for (int k = 0; k < C3_COPY_F4; ++k) {
-        const int i = lane + 64 * k;
-        if (i < all) reinterpret_cast<f4*>(w.rec)[i] = t[k];
-    }
-}
+// the records of a batch: LDS -> stash (the backward takes a record apart as it loads it: see there)
 DEV void c3_store_records(const C3Wave& w, float* __restrict__ dst, int nv) {
     const int lane = threadIdx.x & 63, have = nv * w.rec_floats / 4;
 #pragma unroll
@@ -614,10 +603,53 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_forward_bf_kernel(
 }
 
 // ================================================ backward ==========================================================
+// The input-gradient chain (phases 1 and 4 below) is exact fp32 on v_mfma_f32_16x16x4_f32: its errors travel on, into the first
+// convolution's weight gradient.  The two convolutions' WEIGHT gradients are leaves, and they contract over columns -- 56 and 72 of
+// them per batch of 8 variants: they run as v_mfma_f32_16x16x32_bf16 on two-piece operands (hi = RNE bf16 of the value, mid = RNE bf16
+// of the remainder; products mid.hi + hi.mid + hi.hi in that order, fp32 accumulation: 16 significant bits per operand, relative L2
+// error ~5e-6 whatever the contraction length), like the read-set backward's (pmt_bwd_device.hpp, wgrad_exchange_bf).  The linear's
+// weight gradient contracts over the 8 variants only and stays on the fp32 MFMA.
+//
+// Contraction order: k = 8 * position + variant.  The eight consecutive k a lane (m, kg) feeds into one 32-deep block are then the
+// 8 variants of ONE position 4 b + kg, and a tap shifts the operand by whole positions.  Both operands rest in LDS as fp32
+// "k images" [position][variant >> 2][element 32][variant & 3] (C3T_POS floats per position: 4 floats of padding spread the producers'
+// scattered 4-byte stores over the banks): a lane's operand is two ds_read_b128, 256 contiguous bytes per 16 lanes, and it is split into
+// its pieces in registers (six vector operations per pair) -- bf16 piece images would not fit beside the fp32 arrays the input-gradient
+// chain needs.  The images: a1t, the pooled activations, written from the stash loads and overwritten by phase 4 with d(pooled); dyt,
+// dY2, over the dead a2 array.  The first convolution's other operand, the one-hot of the haplotypes, is exact in one piece and lies
+// as bf16 [input position][channel 16][variant 8] (C3T_OH_POS per position): one ds_read_b128 per (block, offset); the pooled gradient is split by the pool's
+// argmax into two A operands as before.
+#define C3T_POS 260  // floats per position of a k image
+__host__ __device__ constexpr int c3w_max(int a, int b) { return a > b ? a : b; }
+// floats of the backward's per-wave LDS region and of its parts, in this order (every part a multiple of 4 floats = 16 bytes)
+__host__ __device__ constexpr int c3w_a1t_floats(int P1) { return P1 * C3T_POS; }
+__host__ __device__ constexpr int c3w_a2_floats(int V, int ST2) { return c3w_max(V * ST2 * 32, ST2 * C3T_POS); }  // a2 [v][p][32], then dyt
+__host__ __device__ constexpr int c3w_arg_floats(int V, int P1) { return (V * P1 + 3) & ~3; }                      // argmax words [q][v]
+__host__ __device__ constexpr int c3w_x_floats(int V, int ST2) { return V * ST2 * 32; }
+#define C3T_OH_POS(V) (16 * (V) + 8)  // bf16 elements per input position of the one-hot: [channel 16][V] + 16 bytes (its 2-byte stores: apart in the banks)
+__host__ __device__ constexpr int c3w_oh_floats(int V, int S) { return S * C3T_OH_POS(V) / 2; }
+__host__ __device__ constexpr int c3w_floats(int V, int S, int P1, int ST2) {
+    return c3w_a1t_floats(P1) + c3w_a2_floats(V, ST2) + c3w_arg_floats(V, P1) + c3w_x_floats(V, ST2) + V * 16 + c3w_oh_floats(V, S);
+}
+DEV void c3w_read8(const float* p, f4& lo, f4& hi) {  // a lane's 8 variants of one (position, element)
+    lo = *reinterpret_cast<const f4*>(p);
+    hi = *reinterpret_cast<const f4*>(p + 128);
+}
+DEV void c3w_split8(f4 lo, f4 hi, bf8& h, bf8& m) {
+    unsigned hh[4], mm[4], unused = 0u;
+    split_pair<2>(lo[0], lo[1], hh[0], mm[0], unused);
+    split_pair<2>(lo[2], lo[3], hh[1], mm[1], unused);
+    split_pair<2>(hi[0], hi[1], hh[2], mm[2], unused);
+    split_pair<2>(hi[2], hi[3], hh[3], mm[3], unused);
+    h = __builtin_bit_cast(bf8, c3_u4{hh[0], hh[1], hh[2], hh[3]});
+    m = __builtin_bit_cast(bf8, c3_u4{mm[0], mm[1], mm[2], mm[3]});
+}
+
 template <int V, int NW, int K1, int K2, int L2>
 __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
     C3Cfg c, const float* __restrict__ theta, const long long* __restrict__ hap, long long hap_stride, int n, const float* __restrict__ d_out,
     long long d_out_stride, const float* __restrict__ stash, float* __restrict__ gtheta, float* __restrict__ ws, int ws_stride) {
+    static_assert(V == 8, "a lane's eight consecutive k of a 32-deep block are the 8 variants of one position");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const unsigned long long t_begin = C3_TRACE ? __builtin_readcyclecounter() : 0ull;
     const C3Weights W = c3_build_weights(c, theta, lds, true);
@@ -627,11 +659,25 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
     unsigned long long* tr = reinterpret_cast<unsigned long long*>(const_cast<float*>(stash));
     int tr_n = 2;
     const int m = r, kk = g;  // names of the same lane coordinates when the lane feeds an A / B operand: row (or column) m, k-slot kk
-    const C3Wave w = c3_wave_region<V>(c, lds + ((c3_weight_floats(c, true) + 3) & ~3) + wave * c.per_wave);
     const int nbatches = (n + V - 1) / V;
     // the geometry behind the second convolution follows from the template parameters (cnn3_config checks the model against it):
     // compile-time trip counts let the compiler unroll the contraction loops and issue their LDS reads ahead of the matrix core
     constexpr int P1 = L2 + K2 - 1, ST2 = L2 <= 4 ? 4 : 8, N2T = (V * ST2) / 16, NPT = (V * P1 + 15) / 16;
+    constexpr int REC_A2 = P1 * 32, REC_ARG = P1 * 32 + ST2 * 32;  // a record of the stash: [a1: P1 * 32][a2: ST2 * 32][argmax: P1 words]
+    static_assert(ST2 * C3T_POS <= c3w_a2_floats(V, ST2) && V * ST2 * 32 <= c3w_a2_floats(V, ST2), "a2 and the dY2 image share one array");
+    static_assert(C3T_POS % 4 == 0 && C3T_POS >= 256 && c3w_a1t_floats(P1) % 4 == 0 && c3w_a2_floats(V, ST2) % 4 == 0, "16-byte operand reads");
+    static_assert(ST2 % 4 == 0, "a k block is 4 positions");
+    const int S = c.S;
+    // ---- this wave's LDS region (c3w_floats) ----------------------------------------------------------------------------
+    float* const a1t = lds + ((c3_weight_floats(c, true) + 3) & ~3) + wave * c3w_floats(V, S, P1, ST2);
+    float* const a2 = a1t + c3w_a1t_floats(P1);
+    float* const dyt = a2;  // (once a2 is dead)
+    unsigned* const argw = reinterpret_cast<unsigned*>(a2 + c3w_a2_floats(V, ST2));
+    float* const x = reinterpret_cast<float*>(argw) + c3w_arg_floats(V, P1);
+    float* const dout = x + c3w_x_floats(V, ST2);
+    unsigned short* const oh = reinterpret_cast<unsigned short*>(dout + V * 16);
+    for (int i = lane; i < c3w_oh_floats(V, S); i += 64) reinterpret_cast<unsigned*>(oh)[i] = 0u;  // (channels 10 .. 15 stay zero for good)
+    c3_wave_sync();
     // register-resident weight gradients over every variant this wave sees.  C layout: acc[j] of lane (g, col) = row 4 g + j.
     f4 gw1[K1][2], gw2[K2][2][2], gwl[L2][2];  // rows = out channels (position order) | linear outputs; cols below
     f4 gb1[2] = {c3_zero(), c3_zero()}, gb2[2] = {c3_zero(), c3_zero()};  // per-lane partial sums over this lane's columns
@@ -642,18 +688,94 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
     for (int k = 0; k < K2; ++k) gw2[k][0][0] = gw2[k][0][1] = gw2[k][1][0] = gw2[k][1][1] = c3_zero();
 #pragma unroll
     for (int k = 0; k < L2; ++k) gwl[k][0] = gwl[k][1] = c3_zero();
-    for (int batch = blockIdx.x * NW + wave; batch < nbatches; batch += gridDim.x * NW) {
-        const long long v0 = (long long)batch * V;
-        const int nv = (int)min((long long)V, (long long)n - v0);
-        // ---- this batch's inputs: haplotypes, upstream gradient, the forward's stash ------------------------------------
-        c3_load_haplotypes<V>(c, w, hap, hap_stride, v0, nv);
-        c3_load_records<V>(w, stash + (size_t)v0 * c.stash_per, nv);
+    // ---- a batch's inputs: haplotypes, upstream gradient, the forward's stash.  All waves of the device ask for their 18 KB of
+    //      records at the same moment, so the load is bound by the HBM's bandwidth, not its latency (measured: 10 - 12 K of a batch's
+    //      43 K cycles).  The NEXT batch's inputs are therefore requested behind phase 3 and rest in registers under phase 4 (which
+    //      needs few); a2 and d(out) go to LDS behind phase 4, where their arrays are dead, the rest behind phase 5.  Variants beyond
+    //      the end are zeros everywhere, so they add exactly nothing to any sum.
+    constexpr int NA1 = (V * P1 * 8 + 63) / 64, NA2 = (V * ST2 * 8 + 63) / 64, NARG = (V * P1 + 63) / 64;
+    const int n2s = 2 * S;
+    long long hb[C3_HAP_LOADS];
+    f4 t1[NA1], t2[NA2];
+    unsigned ta[NARG];
+    float td[(V * 16) / 64];
+    int nv_req = 0;  // variants of the batch the registers above hold: what the absent ones loaded becomes zeros on the way to LDS
+    auto request = [&](int batch) {
+        // (a2 and d(out) first: they are stored first.  Every lane loads from a valid address -- an absent variant's from the batch's
+        //  first, or from the first of all behind the last batch -- and the stores drop what it got: no branches between the loads,
+        //  and nothing that waits for them here)
+        const int nv = batch < nbatches ? (int)min((long long)V, (long long)n - (long long)batch * V) : 0;
+        const long long v0 = nv > 0 ? (long long)batch * V : 0;
+        const float* src = stash + (size_t)v0 * c.stash_per;
+#pragma unroll
+        for (int k = 0; k < NA2; ++k) {
+            const int i = min(lane + 64 * k, V * ST2 * 8 - 1), v = i / (ST2 * 8), rem = i - v * (ST2 * 8);
+            t2[k] = *reinterpret_cast<const f4*>(src + (size_t)(v < nv ? v : 0) * c.stash_per + REC_A2 + 4 * rem);
+        }
 #pragma unroll
         for (int k = 0; k < (V * 16) / 64; ++k) {
             const int i = lane + 64 * k, v = i >> 4, o = i & 15;
-            w.dout[i] = (v < nv && o < c.O) ? d_out[(size_t)(v0 + v) * d_out_stride + o] : 0.f;
+            td[k] = d_out[(size_t)(v0 + (v < nv ? v : 0)) * d_out_stride + min(o, c.O - 1)];
         }
-        c3_wave_sync();
+#pragma unroll
+        for (int k = 0; k < NA1; ++k) {  // a1: f4 `rem` of variant v's P1 * 8
+            const int i = min(lane + 64 * k, V * P1 * 8 - 1), v = i / (P1 * 8), rem = i - v * (P1 * 8);
+            t1[k] = *reinterpret_cast<const f4*>(src + (size_t)(v < nv ? v : 0) * c.stash_per + 4 * rem);
+        }
+#pragma unroll
+        for (int k = 0; k < C3_HAP_LOADS; ++k) {
+            const int i = min(lane + 64 * k, V * n2s - 1), v = i / n2s, e = i - v * n2s;
+            hb[k] = hap[(size_t)(v0 + (v < nv ? v : 0)) * hap_stride + e];
+        }
+#pragma unroll
+        for (int k = 0; k < NARG; ++k) {
+            const int i = min(lane + 64 * k, V * P1 - 1), v = i / P1, q = i - v * P1;
+            ta[k] = reinterpret_cast<const unsigned*>(src + (size_t)(v < nv ? v : 0) * c.stash_per + REC_ARG)[q];
+        }
+        nv_req = nv;
+    };
+    auto store_a2_dout = [&]() {
+#pragma unroll
+            for (int k = 0; k < NA2; ++k) {
+                const int i = lane + 64 * k;
+                if (i < V * ST2 * 8) reinterpret_cast<f4*>(a2)[i] = i / (ST2 * 8) < nv_req ? t2[k] : c3_zero();
+            }
+#pragma unroll
+            for (int k = 0; k < (V * 16) / 64; ++k) {
+                const int i = lane + 64 * k;
+                dout[i] = ((i >> 4) < nv_req && (i & 15) < c.O) ? td[k] : 0.f;
+            }
+    };
+    auto store_a1_arg_onehot = [&]() {
+#pragma unroll
+            for (int k = 0; k < C3_HAP_LOADS; ++k) {  // one-hot, channel 2 * base + (0 ref | 1 alt) (reference data/batch.py:115-130)
+                const int i = lane + 64 * k, v = i / n2s, e = i - v * n2s, hs = e >= S ? 1 : 0, pos = e - hs * S;
+                if (i < V * n2s) {
+                    unsigned short* dst = oh + pos * C3T_OH_POS(V) + hs * V + v;
+#pragma unroll
+                    for (int bs = 0; bs < 5; ++bs) dst[2 * bs * V] = (hb[k] == bs && v < nv_req) ? (unsigned short)0x3F80 : (unsigned short)0;  // 1.0 as bf16; any other code matches no channel
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NA1; ++k) {
+                const int i = lane + 64 * k, v = i / (P1 * 8), rem = i - v * (P1 * 8), q = rem >> 3, e0 = (rem & 7) * 4;
+                if (i < V * P1 * 8) {
+                    float* dst = a1t + q * C3T_POS + (v >> 2) * 128 + e0 * 4 + (v & 3);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) dst[4 * j] = v < nv_req ? t1[k][j] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NARG; ++k) {
+                const int i = lane + 64 * k, v = i / P1, q = i - v * P1;
+                if (i < V * P1) argw[q * V + v] = v < nv_req ? ta[k] : 0u;
+            }
+    };
+    request(blockIdx.x * NW + wave);
+    store_a2_dout();
+    store_a1_arg_onehot();
+    c3_wave_sync();
+    for (int batch = blockIdx.x * NW + wave; batch < nbatches; batch += gridDim.x * NW) {
         if (C3_TRACE && tracing && lane == 0 && tr_n == 2) { tr[0] = t_begin; tr[1] = t_weights; }
         C3_EV();  // inputs in LDS
         // ---- 1. linear: d(a2) = Wl^T d(out), a column per variant; d(bias) -------------------------------------------------
@@ -661,13 +783,13 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
             const int v = min(r, V - 1);
             f4 bo;  // B operand: k = output o = 4 j + g of variant column r
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bo[j] = (r < V) ? w.dout[v * 16 + 4 * j + g] : 0.f;
+            for (int j = 0; j < 4; ++j) bo[j] = (r < V) ? dout[v * 16 + 4 * j + g] : 0.f;
 #pragma unroll
             for (int p = 0; p < L2; ++p)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const f4 d = c3_mfma4(*reinterpret_cast<const f4*>(W.wltf + ((p * 2 + t) * 64 + lane) * 4), bo, c3_zero());
-                    if (r < V) *reinterpret_cast<f4*>(w.x + (v * ST2 + p) * 32 + 16 * t + 4 * g) = d;  // rows = channels 16 t + 4 j + g
+                    if (r < V) *reinterpret_cast<f4*>(x + (v * ST2 + p) * 32 + 16 * t + 4 * g) = d;  // rows = channels 16 t + 4 j + g
                 }
         }
         c3_wave_sync();
@@ -682,8 +804,8 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
             v = min(v, V - 1);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                float* px = w.x + (v * ST2 + p) * 32 + 16 * t + 4 * g;
-                const f4 y = *reinterpret_cast<const f4*>(w.a2(v, p) + 16 * t + 4 * g);
+                float* px = x + (v * ST2 + p) * 32 + 16 * t + 4 * g;
+                const f4 y = *reinterpret_cast<const f4*>(a2 + (v * ST2 + p) * 32 + 16 * t + 4 * g);
                 f4 d = *reinterpret_cast<const f4*>(px) * c3_act_grad4(c.act2, y);
                 if (!valid) d = c3_zero();
                 if (v < V && col < V * ST2) *reinterpret_cast<f4*>(px) = d;
@@ -694,36 +816,70 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
 #pragma unroll
             for (int s = 0; s < V / 4; ++s) {
                 const int v = 4 * s + kk;
-                const float a = w.dout[v * 16 + m];  // A row m = output o (zero beyond O and beyond nv)
+                const float a = dout[v * 16 + m];  // A row m = output o (zero beyond O and beyond nv)
                 gbl += a;
 #pragma unroll
                 for (int p = 0; p < L2; ++p)
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) gwl[p][t] = mfma16(a, w.a2(v, p)[16 * t + m], gwl[p][t]);  // B col m = element m of the block
+                    for (int t = 0; t < 2; ++t) gwl[p][t] = mfma16(a, a2[(v * ST2 + p) * 32 + 16 * t + m], gwl[p][t]);  // B col m = element m of the block
+            }
+        }
+        c3_wave_sync();  // a2 is dead: the dY2 image takes its place, [position][v >> 2][element][v & 3]
+#pragma unroll
+        for (int T = 0; T < N2T; ++T) {
+            const int col = 16 * T + r, v = col / ST2, p = col - v * ST2;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const f4 d = *reinterpret_cast<const f4*>(x + col * 32 + 16 * t + 4 * g);  // (this lane's own stores of the loop above)
+                float* dst = dyt + p * C3T_POS + (v >> 2) * 128 + (16 * t + 4 * g) * 4 + (v & 3);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dst[4 * j] = d[j];
             }
         }
         c3_wave_sync();
         C3_EV();  // 2 done
-        // ---- 3. second convolution's weight gradient: dW2_k[co][ci] += sum_cols dY2[co][col] a1[ci][col + k] ----------------
+        // ---- 3. second convolution's weight gradient: dW2_k[co][ci] += sum_cols dY2[co][col] a1[ci][col + k], as 32-deep bf16
+        //         products over k = (position, variant): block b holds positions 4 b .. 4 b + 3, this lane feeds position 4 b + kk -----
+        {
+            constexpr int NB = ST2 / 4;
+            f4 ra[NB][2][2], rb[NB][K2][2][2];  // raw fp32 operands: every read is issued before the first product
 #pragma unroll
-        for (int s = 0; s < (V * ST2) / 4; ++s) {
-            const int col = 4 * s + kk;
-            const int v = col / ST2, p = col - v * ST2;
-            const float a0 = w.x[col * 32 + m], a1v = w.x[col * 32 + 16 + m];  // rows = element m of channel block 0 / 1
+            for (int b = 0; b < NB; ++b) {
+                const int p = 4 * b + kk;
 #pragma unroll
-            for (int tap = 0; tap < K2; ++tap) {
-                const float* src = w.a1(v, min(p + tap, P1 - 1)) + m;  // (padding columns: dY2 is zero there)
-                const float b0 = src[0], b1 = src[16];
-                gw2[tap][0][0] = mfma16(a0, b0, gw2[tap][0][0]);
-                gw2[tap][0][1] = mfma16(a0, b1, gw2[tap][0][1]);
-                gw2[tap][1][0] = mfma16(a1v, b0, gw2[tap][1][0]);
-                gw2[tap][1][1] = mfma16(a1v, b1, gw2[tap][1][1]);
+                for (int mt = 0; mt < 2; ++mt) c3w_read8(dyt + p * C3T_POS + (16 * mt + m) * 4, ra[b][mt][0], ra[b][mt][1]);  // rows = element m of channel block mt
+#pragma unroll
+                for (int tap = 0; tap < K2; ++tap)
+#pragma unroll
+                    for (int kt = 0; kt < 2; ++kt)  // (padding positions: dY2 is zero there, a1 only has to be finite)
+                        c3w_read8(a1t + min(p + tap, P1 - 1) * C3T_POS + (16 * kt + m) * 4, rb[b][tap][kt][0], rb[b][tap][kt][1]);
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                bf8 ah[2], am[2];
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) c3w_split8(ra[b][mt][0], ra[b][mt][1], ah[mt], am[mt]);
+#pragma unroll
+                for (int tap = 0; tap < K2; ++tap)
+#pragma unroll
+                    for (int kt = 0; kt < 2; ++kt) {
+                        bf8 bh, bm;
+                        c3w_split8(rb[b][tap][kt][0], rb[b][tap][kt][1], bh, bm);
+#pragma unroll
+                        for (int mt = 0; mt < 2; ++mt) gw2[tap][mt][kt] = mfma_bf16(am[mt], bh, gw2[tap][mt][kt]);
+#pragma unroll
+                        for (int mt = 0; mt < 2; ++mt) gw2[tap][mt][kt] = mfma_bf16(ah[mt], bm, gw2[tap][mt][kt]);
+#pragma unroll
+                        for (int mt = 0; mt < 2; ++mt) gw2[tap][mt][kt] = mfma_bf16(ah[mt], bh, gw2[tap][mt][kt]);
+                    }
             }
         }
         c3_wave_sync();
         C3_EV();  // 3 done
+        request(batch + gridDim.x * NW);  // the next batch's inputs: in flight under phase 4
         // ---- 4. second convolution's input gradient (gather with the transposed weights), through the first activation:
-        //         d(pooled)[v][q] -> written over a1[v][q] (each lane reads its block of a1 before it overwrites it) ---------------
+        //         d(pooled)[v][q] -> written over a1[v][q] in the a1t image (each lane reads its elements of a1 before it overwrites
+        //         them): phase 5's A operand ------------------------------------------------------------------------------------
 #pragma unroll
         for (int T = 0; T < NPT; ++T) {
             const int idx = 16 * T + r;  // flat (variant, pooled position)
@@ -736,7 +892,7 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
             for (int tap = 0; tap < K2; ++tap) {
                 const int p = q - tap;
                 const bool ok = valid && p >= 0 && p < L2;
-                const float* src = w.x + (v * ST2 + (ok ? p : 0)) * 32 + 4 * g;
+                const float* src = x + (v * ST2 + (ok ? p : 0)) * 32 + 4 * g;
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt) {
                     f4 b = *reinterpret_cast<const f4*>(src + 16 * kt);
@@ -749,50 +905,67 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
             if (valid) {
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
-                    float* pa = w.a1(v, q) + 16 * mt + 4 * g;
-                    const f4 d = acc[mt] * c3_act_grad4(c.act1, *reinterpret_cast<const f4*>(pa));
-                    *reinterpret_cast<f4*>(pa) = d;
+                    float* pa = a1t + q * C3T_POS + (v >> 2) * 128 + (16 * mt + 4 * g) * 4 + (v & 3);  // element 16 mt + 4 g + j at pa[4 j]
+                    const f4 d = acc[mt] * c3_act_grad4(c.act1, f4{pa[0], pa[4], pa[8], pa[12]});
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) pa[4 * j] = d[j];
                     gb1[mt] = gb1[mt] + d;  // the pool routes every pooled gradient to exactly one position: d(bias1) = its sum
                 }
             }
         }
         c3_wave_sync();
+        store_a2_dout();  // (a2 / the dY2 image and d(out) are dead; phase 5 reads neither)
         C3_EV();  // 4 done
         // ---- 5. first convolution's weight gradient from the pooled gradient, split by the pool's argmax:
-        //         dW1_k[co][ci] += sum_(v,q) [arg = 0] dP one_hot[2 q + k] + [arg = 1] dP one_hot[2 q + 1 + k] -----------------------
+        //         dW1_k[co][ci] += sum_(q,v) [arg = 0] dP one_hot[2 q + k] + [arg = 1] dP one_hot[2 q + 1 + k], as 32-deep bf16
+        //         products over k = (pooled position, variant): this lane feeds position 4 b + kk of block b (zeros beyond P1) ------
+        {
+            constexpr int NB = (P1 + 3) / 4;
+            f4 ra[NB][2][2];
+            c3_u4 wa[NB][2];       // the pool's argmax words of the 8 variants
+            bf8 bo[NB][K1 + 1];    // one-hot B operands of input positions 2 q .. 2 q + K1: column m = input channel
 #pragma unroll
-        for (int s = 0; s < (V * P1 + 3) / 4; ++s) {
-            const int idx = 4 * s + kk;
-            const bool valid = idx < V * P1;
-            const int ii = valid ? idx : 0;
-            const int v = ii / P1, q = ii - v * P1;
-            const unsigned word = *w.argb(v, q);
-            float a[2][2];  // [argmax][channel block]
+            for (int b = 0; b < NB; ++b) {
+                const int q = min(4 * b + kk, P1 - 1);
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const float d = valid ? w.a1(v, q)[16 * mt + m] : 0.f;
-                const bool second = (word >> (8 * (m >> 2) + 4 * mt + (m & 3))) & 1u;  // byte g' = m >> 2, bit 4 mt + j' (j' = m & 3)
-                a[0][mt] = second ? 0.f : d;
-                a[1][mt] = second ? d : 0.f;
-            }
-            // one-hot B operands of input positions 2 q .. 2 q + K1: column m = input channel (base m >> 1 of the ref / alt haplotype)
-            float oh[K1 + 1];
+                for (int mt = 0; mt < 2; ++mt) c3w_read8(a1t + q * C3T_POS + (16 * mt + m) * 4, ra[b][mt][0], ra[b][mt][1]);
+                wa[b][0] = *reinterpret_cast<const c3_u4*>(argw + q * V);
+                wa[b][1] = *reinterpret_cast<const c3_u4*>(argw + q * V + 4);
 #pragma unroll
-            for (int off = 0; off <= K1; ++off) {
-                oh[off] = 0.f;
-                if (m < 10) {
-                    const int base = w.hap[v * 2 * c.S + (m & 1) * c.S + min(2 * q + off, c.S - 1)];
-                    oh[off] = base == (m >> 1) ? 1.f : 0.f;
-                }
+                for (int off = 0; off <= K1; ++off) bo[b][off] = *reinterpret_cast<const bf8*>(oh + min(2 * q + off, S - 1) * C3T_OH_POS(V) + m * V);
             }
 #pragma unroll
-            for (int tap = 0; tap < K1; ++tap)
+            for (int b = 0; b < NB; ++b) {
+                const bool valid = 4 * b + kk < P1;
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
-                    gw1[tap][mt] = mfma16(a[0][mt], oh[tap], gw1[tap][mt]);
-                    gw1[tap][mt] = mfma16(a[1][mt], oh[tap + 1], gw1[tap][mt]);
+                    const int bit = 8 * (m >> 2) + 4 * mt + (m & 3);  // byte g' = m >> 2, bit 4 mt + j' (j' = m & 3)
+                    f4 a0[2], a1[2];                                  // [variants 0..3 | 4..7] where the first / the second position won
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float d = valid ? ra[b][mt][h][i] : 0.f;
+                            const bool second = (wa[b][h][i] >> bit) & 1u;
+                            a0[h][i] = second ? 0.f : d;
+                            a1[h][i] = second ? d : 0.f;
+                        }
+                    bf8 a0h, a0m, a1h, a1m;
+                    c3w_split8(a0[0], a0[1], a0h, a0m);
+                    c3w_split8(a1[0], a1[1], a1h, a1m);
+#pragma unroll
+                    for (int tap = 0; tap < K1; ++tap) gw1[tap][mt] = mfma_bf16(a0m, bo[b][tap], gw1[tap][mt]);
+#pragma unroll
+                    for (int tap = 0; tap < K1; ++tap) gw1[tap][mt] = mfma_bf16(a0h, bo[b][tap], gw1[tap][mt]);
+#pragma unroll
+                    for (int tap = 0; tap < K1; ++tap) gw1[tap][mt] = mfma_bf16(a1m, bo[b][tap + 1], gw1[tap][mt]);
+#pragma unroll
+                    for (int tap = 0; tap < K1; ++tap) gw1[tap][mt] = mfma_bf16(a1h, bo[b][tap + 1], gw1[tap][mt]);
                 }
+            }
         }
+        c3_wave_sync();
+        store_a1_arg_onehot();
         c3_wave_sync();
         C3_EV();  // 5 done
     }
@@ -986,9 +1159,11 @@ static bool cnn3_config(const PmtModel* m, C3Cfg* c, int V) {
     c->per_wave = (V * c->stash_per + V * c->st2 * 32 + V * 16 + hap_floats + 3) & ~3;
     return true;
 }
+// (the forward's waves take C3Cfg.per_wave, the backward's c3w_floats: its k images and the one-hot are no part of the forward's size)
 static size_t cnn3_lds_bytes(const C3Cfg* c, bool backward, int nw) {
     const int wf = backward ? c->K2 * 4 * 256 + c->L2 * 2 * 256 : c->K1 * 2 * 256 + c->K2 * 4 * 256 + c->L2 * 2 * 256 + 80;
-    return ((size_t)((wf + 3) & ~3) + (size_t)nw * c->per_wave) * sizeof(float);
+    const int per_wave = backward ? c3w_floats(C3_BWD_V, c->S, c->P1, c->st2) : c->per_wave;
+    return ((size_t)((wf + 3) & ~3) + (size_t)nw * per_wave) * sizeof(float);
 }
 static bool cnn3_covers(const PmtModel* m, C3Cfg* fwd, C3Cfg* bwd) {
     return cnn3_config(m, fwd, C3_FWD_V) && cnn3_config(m, bwd, C3_BWD_V) && cnn3_lds_bytes(fwd, false, C3_FWD_NW) <= 160 * 1024 &&
