@@ -1127,7 +1127,10 @@ int pmt_cnn_bn_backward_full(const PmtModel* model_host, const PmtModel* model_d
 
 /* Global-norm clip + AdamW over the flat parameter buffer, one launch sequence, no host sync.
  * Replaces nn.utils.clip_grad_norm_(max_norm=1.0) + torch.optim.AdamW.step (reference misc_utils.py:128-129).
- * `scratch` holds >= 1024 floats.  grad_norm_out (device, optional) receives the pre-clip global L2 norm. */
+ * `scratch` holds >= 1024 floats: a launch writes one partial sum per workgroup (at most 256, one per 1024 elements) to its
+ * first slots and, with PMT_STEP_ON_DEVICE, increments the int32 at PMT_STEP_SLOT; nothing else.  grad_norm_out (device,
+ * optional) receives the pre-clip global L2 norm.  max_grad_norm <= 0: no clipping.  n = 0 launches nothing: theta, the
+ * moments, grad_norm_out and, with PMT_STEP_ON_DEVICE, the step slot are left as they are (an empty update is not a step). */
 int pmt_clip_adamw(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    const PmtAdamW* hyper, float* scratch, float* grad_norm_out, void* stream);
 

@@ -16,6 +16,7 @@
 
 #define PHI_THREADS 256
 #define PHI_MAXN (2 * PMT_MAX_ORTHO_DIM)  // the adjoint works on a 2n x 2n block matrix
+#define PHI_MAX_SQUARINGS 1100            // of expm_inplace: above the exponent of any finite double
 
 __device__ double block_max(double v, double* red) {
     const int tid = threadIdx.x;
@@ -71,8 +72,14 @@ __device__ void expm_inplace(double* S, double* B, double* P, double* T, int N, 
     if (threadIdx.x < N)
         for (int i = 0; i < N; ++i) colsum += fabs(S[i * N + threadIdx.x]);
     const double norm1 = block_max(colsum, red);
+    // A non-finite entry (a loaded checkpoint) makes the norm infinite: no scaling then, and the non-finite values fall out of the series,
+    // where an unbounded count would be 2^31 dependent products in one workgroup.  The count is bounded as a double, above any finite
+    // double's exponent, before it is converted (norm1 / 0.5 itself may overflow).
     int s = 0;
-    if (norm1 > 0.5) s = (int)ceil(log2(norm1 / 0.5));
+    if (norm1 > 0.5 && norm1 <= 1.7976931348623157e308) {
+        const double sq = ceil(log2(norm1 / 0.5));
+        s = sq < (double)PHI_MAX_SQUARINGS ? (int)sq : PHI_MAX_SQUARINGS;
+    }
     const double scale = ldexp(1.0, -s);
     for (int idx = threadIdx.x; idx < N * N; idx += PHI_THREADS) {
         const double b = S[idx] * scale;
