@@ -808,6 +808,68 @@ typedef struct PmtAnnotateArgs {
  * non-empty table, an element width other than 2 / 4 / 8, first_column < 0 or a row shorter than first_column + 7, or a threads_hint not listed: PMT_E_INVALID, nothing launched. */
 int pmt_annotate_sites(const PmtAnnotateArgs* args, void* stream);
 
+/* The normalisation of preprocess_dataset (reference data/plain_text_data.py:205-479: `normalized_data_generator`,
+ * `make_read_quantile_transform`, `normalize_raw_data_list`; sklearn's QuantileTransformer and numpy's nanpercentile / interp behind
+ * them).  The reference builds a Datum per variant, stacks a chunk's reads, fits one QuantileTransformer per chunk on the fragment
+ * length (raw read column 6) of the chunk's REF reads and walks the chunk once more with np.median per variant.  Here the raw arrays of
+ * a slab of whole chunks lie on the device and two entries do the rest.
+ *   Raw arrays (what permutect_amd/data/plain_text_data.py reads from the text): int rows [num_data, int_row_stride] int16 (REF_COUNT,
+ *   ALT_COUNT, ORIGINAL_DEPTH, ORIGINAL_ALT_COUNT = columns 0, 1, 5, 6), float rows [num_data, 17] float16 bits (six scalars, eleven
+ *   info numbers), reads [num_reads, 9 + k] float16 bits (k = num_error_columns), read_start [num_data + 1] CSR offsets (per datum its
+ *   ref rows, then its alt rows), chunk_of [num_data] the chunk of every datum, 0 <= chunk < num_chunks.
+ *   The fit (:238-264, sklearn _dense_fit): per chunk, counts [num_chunks, 65536] tallies the ref reads' column 6 by its 16-bit
+ *   pattern made order-preserving (sign set: 0xFFFF - bits, else bits + 0x8000; -0 counts as +0, a NaN is left out as nanpercentile
+ *   leaves it out) with 32-bit integer atomics; one workgroup per chunk scans its table and takes, for i < nq = min(100, n), the order
+ *   statistics around (n - 1) * ((r_i * 100) / 100), r = linspace(0, 1, nq), interpolates them as numpy's _lerp does (the difference of
+ *   the two float16 neighbours is itself a float16; a + d * t, and b - d * (1 - t) where t >= 0.5; in double, nothing fused) and applies
+ *   the running maximum.  quantiles [num_chunks, 100] (entries from nq on are NaN), ref_reads [num_chunks] = n.  ALL ref reads count:
+ *   the reference's fit subsamples 10 000 of them with an unseeded generator beyond that number, and is identical up to it.
+ *   The reads (:381-453): out_reads [num_reads, 12]: seven bytes of 10 + 3k bits, first bit highest as np.packbits packs them; four
+ *   bytes of tanh(x / 20) of raw columns 4, 5, 7, 8 and one of the quantile-transformed column 6, each clip(v * 32 + 128, 0, 255)
+ *   truncated, with every float16 rounding point of the reference's chain: the quotient, the tanh (double, rounded once), the product,
+ *   the sum.  The transform is sklearn's _transform_col: np.interp's rule in both directions in double (nothing fused), the uniform
+ *   value rounded to float16, 1 / 0 at the bounds (float16(x +- float16(1e-7)) against the end quantiles), then ppf_table: the
+ *   clipped normal quantile as float16 bits for every float16 pattern 0 .. 0x3C00 of the uniform value.  A NaN in column 6 gives byte 0.
+ *   The float rows (:293-379, :455-476): out_floats [num_data, 59 + 3k] float16 bits: the six scalars, 37 indicator / scaled columns
+ *   and the quality feature from lgamma_table (torch.lgamma of every int16 value v as float32 at [v + 32768]), the medians of the five
+ *   float columns and the means of the 10 + 3k boolean columns over the datum's alt reads (np.median: the float16 mean of the two
+ *   middle values of an even count; np.mean of booleans: a double).
+ * fault [1] int32 (zeroed by the entry): 1 + the largest index of a datum whose counts the kernels refuse -- more than 15 alt reads,
+ * none at all, a negative ref count, or read_start not in step with them; such a datum's float row is not written. */
+#define PMT_PREPROCESS_QUANTILES 100
+#define PMT_PREPROCESS_KEYS 65536
+#define PMT_PREPROCESS_PPF 15361
+#define PMT_PREPROCESS_MAX_ALT 15
+#define PMT_PREPROCESS_READ_BYTES 12
+typedef struct PmtPreprocessArgs {
+    int64_t num_data, num_reads;               /* each up to 2^31 - 1 */
+    int64_t int_row_stride;                    /* in elements, >= 7 */
+    int32_t num_chunks, num_error_columns;     /* k: 13, 14 or 15 (10 + 3k bits fill seven bytes) */
+    int32_t threads_hint, reserved;            /* workgroup size of the per-read and per-datum kernels: 64 / 128 / 256 / 512, 0 = 256 */
+    const int16_t* int_rows;
+    const uint16_t* float_rows;                /* [num_data, 17] */
+    const uint16_t* reads;                     /* [num_reads, 9 + k] */
+    const int64_t* read_start;                 /* [num_data + 1] */
+    const int32_t* chunk_of;                   /* [num_data] */
+    uint32_t* counts;                          /* [num_chunks, 65536] workspace of the fit (zeroed by it) */
+    double* quantiles;                         /* [num_chunks, 100]: out of the fit, in of the normalisation */
+    int64_t* ref_reads;                        /* [num_chunks]: likewise */
+    const float* lgamma_table;                 /* [65536] */
+    const uint16_t* ppf_table;                 /* [15361] */
+    uint8_t* out_reads;                        /* [num_reads, 12] */
+    uint16_t* out_floats;                      /* [num_data, 59 + 3k] */
+    int32_t* fault;                            /* [1] */
+} PmtPreprocessArgs;
+/* Three launches on `stream` (a memset of the table, the tally over the reads, a workgroup per chunk); nothing is read back.  Needs
+ * int_rows, reads, read_start, chunk_of, counts, quantiles, ref_reads.  A chunk without a ref read gets n = 0 and a row of NaN: the
+ * caller refuses such a slab before it calls (the reference dies inside sklearn).  num_data == 0: PMT_OK, nothing launched. */
+int pmt_preprocess_fit(const PmtPreprocessArgs* args, void* stream);
+/* Two launches on `stream` (a lane per read; a lane per datum), then ONE word read back after a synchronise of `stream`: PMT_E_CAPACITY
+ * when `fault` is set (above).  Needs every pointer but counts.  num_data == 0: PMT_OK, nothing launched.
+ * Both entries: a NULL struct or needed pointer, sizes < 0 or beyond 2^31 - 1, num_chunks < 1, k outside 13 .. 15, a row stride below 7
+ * or a threads_hint not listed: PMT_E_INVALID, nothing launched.  Bit-identical for any workgroup size and from run to run. */
+int pmt_preprocess_normalize(const PmtPreprocessArgs* args, void* stream);
+
 /* The tallies of an evaluation step (reference metrics/evaluation_metrics.py:49-66 -> AccuracyMetrics, metrics/loss_metrics.py:226-243;
  * training/model_training.py:204-228 runs it three times per parent batch after every validation epoch): the weights of the LABELED
  * variants over (source, label, variant type, ref-count bin, alt-count bin, LOGIT bin) and, per label, the weight called artifact / not

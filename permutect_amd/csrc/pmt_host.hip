@@ -45,6 +45,7 @@ extern "C" int pmt_struct_bytes(int which) {
         case 20: return (int)sizeof(PmtWorstArgs);
         case 21: return (int)sizeof(PmtPosteriorEvalArgs);
         case 22: return (int)sizeof(PmtAnnotateArgs);
+        case 23: return (int)sizeof(PmtPreprocessArgs);
         default: return PMT_E_INVALID;
     }
 }

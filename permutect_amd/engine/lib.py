@@ -246,6 +246,16 @@ class PmtAnnotateArgs(C.Structure):
                 ("normal_mafs", vp), ("keep", vp), ("counters", vp)]
 
 
+class PmtPreprocessArgs(C.Structure):
+    _fields_ = [("num_data", i64), ("num_reads", i64), ("int_row_stride", i64), ("num_chunks", i32), ("num_error_columns", i32),
+                ("threads_hint", i32), ("reserved", i32), ("int_rows", vp), ("float_rows", vp), ("reads", vp), ("read_start", vp),
+                ("chunk_of", vp), ("counts", vp), ("quantiles", vp), ("ref_reads", vp), ("lgamma_table", vp), ("ppf_table", vp),
+                ("out_reads", vp), ("out_floats", vp), ("fault", vp)]
+
+
+# PMT_PREPROCESS_QUANTILES, _KEYS, _PPF, _MAX_ALT, _READ_BYTES
+PREPROCESS_QUANTILES, PREPROCESS_KEYS, PREPROCESS_PPF, PREPROCESS_MAX_ALT, PREPROCESS_READ_BYTES = 100, 65536, 15361, 15, 12
+
 WORST_MAX_QUEUE, WORST_HEADER_WORDS = 1024, 16  # PMT_WORST_MAX_QUEUE, PMT_WORST_HEADER_WORDS
 
 PRUNE_NO_ARTIFACT, PRUNE_NO_NONARTIFACT, PRUNE_CONFUSION_COLUMN, PRUNE_RATES_SUM_TO_ONE, PRUNE_LEVEL_RANGE = 1, 2, 4, 8, 16
@@ -256,7 +266,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_annotate_sites", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_annotate_sites", "pmt_preprocess_fit", "pmt_preprocess_normalize", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -336,6 +346,8 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_worst_record.argtypes = [P(PmtWorstArgs), vp, vp, vp]
     lib.pmt_worst_merge.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.pmt_annotate_sites.argtypes = [P(PmtAnnotateArgs), vp]
+    lib.pmt_preprocess_fit.argtypes = [P(PmtPreprocessArgs), vp]
+    lib.pmt_preprocess_normalize.argtypes = [P(PmtPreprocessArgs), vp]
     lib.pmt_plan_groups_split.argtypes = [vp, vp, i32, vp, vp, i32, P(i32)]
     lib.pmt_layered_scratch_floats.argtypes = [P(PmtModel), i64, i32]
     lib.pmt_layered_scratch_floats.restype = C.c_size_t
@@ -381,7 +393,7 @@ def load(path: str = None) -> C.CDLL:
     for which, st in enumerate([PmtModel, PmtBatch, PmtOutputs, PmtOutputGrads, PmtAdamW, PmtLinear, PmtOp, PmtMlp,
                                 PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs,
                                 PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs, PmtPosteriorEvalArgs,
-                                PmtAnnotateArgs]):
+                                PmtAnnotateArgs, PmtPreprocessArgs]):
         if lib.pmt_struct_bytes(which) != C.sizeof(st):
             raise PmtError(f"ctypes layout of {st.__name__} ({C.sizeof(st)} B) does not match the library "
                            f"({lib.pmt_struct_bytes(which)} B)")

@@ -52,6 +52,7 @@ from permutect_amd.tools.posterior_data import make_posterior_mmap
 from permutect_amd.training.distributed import init_from_env
 
 TEST_DATASET_TAR_NAME = "test_dataset_tar"
+TEST_DATASET_NAME = "test_dataset"      # (reference constants.py: TEST_DATASET_NAME)
 ARTIFACT_MODEL_NAME = "artifact_model"  # (reference constants.py: ARTIFACT_MODEL_NAME)
 GENOMIC_SPAN_NAME = "genomic_span"       # (reference constants.py: GENOMIC_SPAN_NAME)
 CONTIGS_TABLE_NAME = "contigs_table"             # (reference constants.py: CONTIGS_TABLE_NAME)
@@ -66,7 +67,7 @@ def main_without_parsing(args, log=print):
         raise RuntimeError("permutect_amd filters on an MI355X (ROCm device 'cuda'); there is no CPU path")
     dist, rank, world, device = init_from_env()  # this rank's card and the process group, before anything else touches the GPU
     model, _, _ = load_model(getattr(args, ARTIFACT_MODEL_NAME), device=device)
-    data = MemoryMappedData.load_from_tarfile(getattr(args, TEST_DATASET_TAR_NAME))
+    data = load_candidates(args, device)
     if getattr(args, constants.INPUT_NAME, None) is not None:
         data = annotate_candidates(args, data, device, log if rank == 0 else (lambda *a, **k: None))
     dataset = ReadsDataset(data)
@@ -83,6 +84,17 @@ def main_without_parsing(args, log=print):
     if dist is not None:
         dist.barrier()
     return posterior
+
+
+def load_candidates(args, device) -> MemoryMappedData:
+    """--test_dataset_tar, or --test_dataset: the text preprocessed in memory (data/plain_text_data.py)"""
+    tar, text = getattr(args, TEST_DATASET_TAR_NAME, None), getattr(args, TEST_DATASET_NAME, None)
+    if (tar is None) == (text is None):
+        raise ValueError(f"exactly one of --{TEST_DATASET_TAR_NAME} and --{TEST_DATASET_NAME} is required")
+    if tar is not None:
+        return MemoryMappedData.load_from_tarfile(tar)
+    from permutect_amd.data.plain_text_data import make_normalized_mmap_data
+    return make_normalized_mmap_data([text], device=device)
 
 
 def annotate_candidates(args, data: MemoryMappedData, device, log=print) -> MemoryMappedData:
@@ -182,7 +194,10 @@ def run_evaluation(args, posterior: MemoryMappedData, rows, model, thresholds, f
 
 def parse_arguments(argv=None):
     parser = argparse.ArgumentParser(description="the artifact-model stage of filter_variants on an MI355X: candidates -> posterior data")
-    parser.add_argument("--" + TEST_DATASET_TAR_NAME, type=str, required=True, help="dataset tar (the reference's format) of the candidates")
+    source = parser.add_mutually_exclusive_group(required=True)
+    source.add_argument("--" + TEST_DATASET_TAR_NAME, type=str, help="dataset tar (the reference's format) of the candidates")
+    source.add_argument("--" + TEST_DATASET_NAME, type=str, help="Mutect2's plain-text dataset of the candidates, preprocessed in memory "
+                        "(what preprocess_dataset would write to a tar)")
     parser.add_argument("--" + ARTIFACT_MODEL_NAME, type=str, required=True, help="artifact model from train_artifact_model (.pt, the reference's format)")
     parser.add_argument("--" + constants.OUTPUT_NAME, type=str, required=True, help="output tar of the posterior data")
     parser.add_argument("--" + constants.BATCH_SIZE_NAME, type=int, default=DEFAULT_BATCH_SIZE, required=False, help="batch size")
