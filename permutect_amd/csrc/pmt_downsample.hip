@@ -6,7 +6,10 @@
 // launches and a host sync per training step.  Here: one launch decides fractions and new counts, one (after the
 // exclusive scans of the counts) writes the gather index the kernels consume; the decisions come from a counter-based
 // generator keyed by (seed, row), so both launches agree without storing a mask and nothing returns to the host.
-// The random STREAM differs from torch's, the distribution does not (tests/test_downsample_gpu.py).
+// The random STREAM differs from torch's, the distribution does not (tests/test_downsample_gpu.py).  The draws themselves are
+// pinned exactly: tests/downsample_cases.py restates this file's arithmetic on the host, tests/test_downsample_mirror_cpu.py holds
+// that mirror against the reference's scheme, and tests/test_downsample_exact_gpu.py holds every fraction, count and index row of
+// these kernels against the mirror, bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
