@@ -1,10 +1,10 @@
 // Haplotype CNN, batched-column kernels: the production-shaped stack
 //     Conv1d(10 -> C1, k1) -> MaxPool1d(2) -> act -> Conv1d(C1 -> C2, k2) -> act -> Flatten -> Linear(C2 * L2 -> O)
 // (reference architecture/dna_sequence_convolution.py:31-111 on the one-hot of data/batch.py:115-130) as plain GEMMs on the
-// matrix core.  The fp32 forward and the backward's input-gradient chain run on v_mfma_f32_16x16x4_f32 (exact fp32, like the
-// reference); the production forward runs fp32-equivalent products on two f16 pieces per operand; the backward's convolution
-// WEIGHT gradients, leaves whose rounding goes no further, run 32-deep bf16 products on two pieces per operand (16 significant
-// bits, ~2e-6 relative L2 on the gradient; see "backward" below).
+// matrix core.  The fp32 forward runs on v_mfma_f32_16x16x4_f32 (exact fp32, like the reference); the production forward runs
+// fp32-equivalent products on two f16 pieces per operand; the backward's convolution weight gradients AND its input-gradient
+// chain run 32-deep bf16 products on two pieces per operand (16 significant bits, 3 - 8e-6 relative L2 on the gradient; see
+// "backward" below); only the linear's weight gradient, 8 deep, stays on the fp32 MFMA.
 //
 // pmt_cnn2.hip gives a wave ONE variant: a convolution's 7 or 19 output positions half-fill its 16-column tiles, every B
 // operand is an im2col gather through a tap table (~10 instructions per element) and the input gradient is a col2im of LDS
@@ -60,6 +60,8 @@ DEV void c3_wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 DEV int c3_row(int m) { return 4 * (m & 3) + (m >> 2); }  // A-fragment row m / block element e -> channel within the 16-block
+DEV int c3_chan_of_elem(int e) { return 16 * (e >> 4) + 4 * (e & 3) + ((e & 15) >> 2); }  // record element -> channel
+typedef unsigned c3_u4 __attribute__((ext_vector_type(4)));
 DEV float c3_act(int kind, float x) { return kind == PMT_CNN_LEAKY_RELU ? fmaxf(x, 0.01f * x) : selu1(x); }  // (max: x for x > 0, 0.01 x below)
 DEV float c3_act_grad(int kind, float y) { return kind == PMT_CNN_LEAKY_RELU ? (y > 0.f ? 1.f : 0.01f) : selu_grad_from_out(y); }
 DEV f4 c3_act4(int kind, f4 v) { return f4{c3_act(kind, v[0]), c3_act(kind, v[1]), c3_act(kind, v[2]), c3_act(kind, v[3])}; }
@@ -77,7 +79,10 @@ DEV f4 c3_dpp4(f4 v) { return f4{dpp_mov<CTRL>(v[0]), dpp_mov<CTRL>(v[1]), dpp_m
 // fragment element [lane = 16 g + m][j]: row = 16 mt + c3_row(m), k = 16 kt + 4 j + g   (pmt_device.hpp's convention)
 struct C3Weights {
     const float *w1f, *w2f, *wlf;     // forward:  [K1][2][256], [K2][2 mt][2 kt][256], [L2][2][256]
-    const float *w2tf, *wltf;         // backward: W2^T [K2][2 mt = ci][2 kt = co][256], Wl^T [L2][2][256] (rows = channels, k = outputs)
+    // backward: A fragments of the 32-deep bf16 products in two pieces (hi = RNE bf16 of the weight, mid = RNE bf16 of the remainder),
+    // lane (m, kg) holds k = 8 kg + i: W2^T [K2][2 mt = ci][piece][64 lanes] (k = out channel of record element 8 kg + i),
+    // Wl^T [L2][2 t][piece][32 lanes] (rows = channels, k = output 8 kg + i; the 16 outputs are lanes kg < 2: see phase 1)
+    const c3_u4 *w2tp, *wltp;
     const float *b1p, *b2p, *blp;     // biases in position order (element 4 g + j = feature 4 j + g): [2][16], [2][16], [16]
 };
 DEV int c3_weight_floats(const C3Cfg& c, bool backward) {
@@ -119,19 +124,41 @@ DEV C3Weights c3_build_weights(const C3Cfg& c, const float* __restrict__ theta, 
         }
         W.w1f = w1f; W.w2f = w2f; W.wlf = wlf; W.b1p = bp; W.b2p = bp + 32; W.blp = bp + 64;
     } else {
-        float* w2tf = cur; cur += c.K2 * 4 * 256;
-        for (int i = tid; i < c.K2 * 4 * 256; i += nthr) {
-            const int j = i & 3, lane = (i >> 2) & 63, kt = (i >> 8) & 1, mt = (i >> 9) & 1, tap = i >> 10;
-            const int ci = 16 * mt + c3_row(lane & 15), co = 16 * kt + 4 * j + (lane >> 4);
-            w2tf[i] = (co < c.C2 && ci < c.C1) ? theta[c.w2 + (co * c.C1 + ci) * c.K2 + tap] : 0.f;
+        c3_u4* w2tp = reinterpret_cast<c3_u4*>(cur); cur += c.K2 * 4 * 256;
+        for (int e = tid; e < c.K2 * 2 * 64; e += nthr) {
+            const int ln = e & 63, mt = (e >> 6) & 1, tap = e >> 7, ci = 16 * mt + c3_row(ln & 15), kg = ln >> 4;
+            unsigned h[4], md[4], unused = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float v[2];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int co = c3_chan_of_elem(8 * kg + 2 * q + s);
+                    v[s] = (co < c.C2 && ci < c.C1) ? theta[c.w2 + (co * c.C1 + ci) * c.K2 + tap] : 0.f;
+                }
+                split_pair<2>(v[0], v[1], h[q], md[q], unused);
+            }
+            w2tp[((tap * 2 + mt) * 2 + 0) * 64 + ln] = c3_u4{h[0], h[1], h[2], h[3]};
+            w2tp[((tap * 2 + mt) * 2 + 1) * 64 + ln] = c3_u4{md[0], md[1], md[2], md[3]};
         }
-        float* wltf = cur; cur += c.L2 * 2 * 256;
-        for (int i = tid; i < c.L2 * 2 * 256; i += nthr) {
-            const int j = i & 3, lane = (i >> 2) & 63, t = (i >> 8) & 1, p = i >> 9;
-            const int ch = 16 * t + c3_row(lane & 15), o = 4 * j + (lane >> 4);
-            wltf[i] = (o < c.O && ch < c.C2) ? theta[c.wl + o * c.F + ch * c.L2 + p] : 0.f;
+        c3_u4* wltp = reinterpret_cast<c3_u4*>(cur); cur += c.L2 * 2 * 256;
+        for (int e = tid; e < c.L2 * 2 * 32; e += nthr) {
+            const int ln = e & 31, t = (e >> 5) & 1, p = e >> 6, ch = 16 * t + c3_row(ln & 15), kg = ln >> 4;
+            unsigned h[4], md[4], unused = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float v[2];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int o = 8 * kg + 2 * q + s;
+                    v[s] = (o < c.O && ch < c.C2) ? theta[c.wl + o * c.F + ch * c.L2 + p] : 0.f;
+                }
+                split_pair<2>(v[0], v[1], h[q], md[q], unused);
+            }
+            wltp[((p * 2 + t) * 2 + 0) * 32 + ln] = c3_u4{h[0], h[1], h[2], h[3]};
+            wltp[((p * 2 + t) * 2 + 1) * 32 + ln] = c3_u4{md[0], md[1], md[2], md[3]};
         }
-        W.w2tf = w2tf; W.wltf = wltf;
+        W.w2tp = w2tp; W.wltp = wltp;
     }
     __syncthreads();
     return W;
@@ -355,8 +382,6 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_forward_kernel(
 //   * a training forward writes its records (fp32 a1, a2, pool argmax: the backward's format) straight from registers.
 // Selected for K1 * 10 <= 32 (PmtModel.cnn_debug bit 8 keeps the fp32 kernel above: A/B runs, and the parity tests run both).
 #define C3B_OH_PAD 16
-DEV int c3_chan_of_elem(int e) { return 16 * (e >> 4) + 4 * (e & 3) + ((e & 15) >> 2); }  // record element -> channel
-typedef unsigned c3_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned c3_u2 __attribute__((ext_vector_type(2)));
 // Round 4: the pieces are TWO f16 values per operand with the low one scaled by 2^12 (pmt_device.hpp, linear_acc_f16: fp32-equivalent
 // like three bf16 pieces) -- three MFMAs per product instead of six (conv1: two instead of three), five vector operations per
@@ -603,19 +628,31 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_forward_bf_kernel(
 }
 
 // ================================================ backward ==========================================================
-// The input-gradient chain (phases 1 and 4 below) is exact fp32 on v_mfma_f32_16x16x4_f32: its errors travel on, into the first
-// convolution's weight gradient.  The two convolutions' WEIGHT gradients are leaves, and they contract over columns -- 56 and 72 of
-// them per batch of 8 variants: they run as v_mfma_f32_16x16x32_bf16 on two-piece operands (hi = RNE bf16 of the value, mid = RNE bf16
-// of the remainder; products mid.hi + hi.mid + hi.hi in that order, fp32 accumulation: 16 significant bits per operand, relative L2
-// error ~5e-6 whatever the contraction length), like the read-set backward's (pmt_bwd_device.hpp, wgrad_exchange_bf).  The linear's
-// weight gradient contracts over the 8 variants only and stays on the fp32 MFMA.
+// Every product but the linear's weight gradient runs as v_mfma_f32_16x16x32_bf16 on two-piece operands (hi = RNE bf16 of the value,
+// mid = RNE bf16 of the remainder; products mid.hi + hi.mid + hi.hi in that order, fp32 accumulation: 16 significant bits per operand,
+// relative L2 error ~5e-6 whatever the contraction length), like the read-set backward's (pmt_bwd_device.hpp, wgrad_exchange_bf).  The
+// linear's weight gradient contracts over the 8 variants only and stays on the fp32 MFMA.
 //
+// The input-gradient chain (phases 1 and 4 below) contracts over channels, with the weights as the stationary A operand: their
+// transposed piece fragments are built once per workgroup (c3_build_weights) and stay in LDS.
+//   * phase 1, d(a2) = Wl^T d(out): k = the linear's output, 16 at most.  That is HALF a 32-deep block: the B operand (d(out), split in
+//     registers once per batch) is zero at k >= 16, and the same 32-deep opcode runs -- a 16-deep MFMA onto a 32-deep one's accumulator
+//     is the hazard of scripts/check_mfma_chains.py.  The weights' fragments exist for k < 16 only (lanes kg < 2; the others read the
+//     same finite words against B's zeros).
+//   * phase 4, d(pooled) = sum over taps W2_tap^T dY2[q - tap]: k = conv2's 32 output channels, one block per tap.  dY2 rests in the x
+//     array as bf16 pieces [column][piece][32 record elements] (phase 2 splits each value once; the array held phase 1's fp32 d(a2)
+//     until then): a B operand is one ds_read_b128 per piece.  A tap that reaches outside the L2 positions reads the column's padding
+//     position L2 < ST2, which phase 2 leaves zero.
+// The chain's rounding travels on into the first convolution's weight gradient: measured in profiles/cnn3_backward_chain_bf16.txt.
+//
+// The two convolutions' WEIGHT gradients contract over columns -- 56 and 72 of them per batch of 8 variants.
 // Contraction order: k = 8 * position + variant.  The eight consecutive k a lane (m, kg) feeds into one 32-deep block are then the
 // 8 variants of ONE position 4 b + kg, and a tap shifts the operand by whole positions.  Both operands rest in LDS as fp32
 // "k images" [position][variant >> 2][element 32][variant & 3] (C3T_POS floats per position: 4 floats of padding spread the producers'
 // scattered 4-byte stores over the banks): a lane's operand is two ds_read_b128, 256 contiguous bytes per 16 lanes, and it is split into
-// its pieces in registers (six vector operations per pair) -- bf16 piece images would not fit beside the fp32 arrays the input-gradient
-// chain needs.  The images: a1t, the pooled activations, written from the stash loads and overwritten by phase 4 with d(pooled); dyt,
+// its pieces in registers (six vector operations per pair) -- bf16 piece images of both would not fit beside the arrays that exist (a1t
+// is read as fp32 by phase 4's activation gradient, a2 by the linear's weight gradient).
+// The images: a1t, the pooled activations, written from the stash loads and overwritten by phase 4 with d(pooled); dyt,
 // dY2, over the dead a2 array.  The first convolution's other operand, the one-hot of the haplotypes, is exact in one piece and lies
 // as bf16 [input position][channel 16][variant 8] (C3T_OH_POS per position): one ds_read_b128 per (block, offset); the pooled gradient is split by the pool's
 // argmax into two A operands as before.
@@ -625,7 +662,12 @@ __host__ __device__ constexpr int c3w_max(int a, int b) { return a > b ? a : b; 
 __host__ __device__ constexpr int c3w_a1t_floats(int P1) { return P1 * C3T_POS; }
 __host__ __device__ constexpr int c3w_a2_floats(int V, int ST2) { return c3w_max(V * ST2 * 32, ST2 * C3T_POS); }  // a2 [v][p][32], then dyt
 __host__ __device__ constexpr int c3w_arg_floats(int V, int P1) { return (V * P1 + 3) & ~3; }                      // argmax words [q][v]
-__host__ __device__ constexpr int c3w_x_floats(int V, int ST2) { return V * ST2 * 32; }
+// one column of x: 32 floats of d(a2), then [piece 2][32 elements] of dY2 in bf16, and 16 bytes of padding: at 128 bytes from column to
+// column the sixteen columns of a tile start in ONE bank, and every 8- or 16-byte access of phases 2 and 4 queued 16 deep there
+// (measured: phase 2 7 400 -> 4 200 cycles, phase 4 10 200 -> 9 400, the kernel 114.8 -> 108.0 us)
+#define C3X_COL 144
+#define C3X_F (C3X_COL / 4)
+__host__ __device__ constexpr int c3w_x_floats(int V, int ST2) { return V * ST2 * C3X_F; }
 #define C3T_OH_POS(V) (16 * (V) + 8)  // bf16 elements per input position of the one-hot: [channel 16][V] + 16 bytes (its 2-byte stores: apart in the banks)
 __host__ __device__ constexpr int c3w_oh_floats(int V, int S) { return S * C3T_OH_POS(V) / 2; }
 __host__ __device__ constexpr int c3w_floats(int V, int S, int P1, int ST2) {
@@ -674,6 +716,7 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
     float* const dyt = a2;  // (once a2 is dead)
     unsigned* const argw = reinterpret_cast<unsigned*>(a2 + c3w_a2_floats(V, ST2));
     float* const x = reinterpret_cast<float*>(argw) + c3w_arg_floats(V, P1);
+    unsigned char* const xp = reinterpret_cast<unsigned char*>(x);  // (x as dY2's bf16 pieces: phases 2 -> 4)
     float* const dout = x + c3w_x_floats(V, ST2);
     unsigned short* const oh = reinterpret_cast<unsigned short*>(dout + V * 16);
     for (int i = lane; i < c3w_oh_floats(V, S); i += 64) reinterpret_cast<unsigned*>(oh)[i] = 0u;  // (channels 10 .. 15 stay zero for good)
@@ -781,34 +824,37 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
         // ---- 1. linear: d(a2) = Wl^T d(out), a column per variant; d(bias) -------------------------------------------------
         {
             const int v = min(r, V - 1);
-            f4 bo;  // B operand: k = output o = 4 j + g of variant column r
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bo[j] = (r < V) ? dout[v * 16 + 4 * j + g] : 0.f;
+            // B operand: k = output o = 8 kk + i of variant column r; zero at k >= 16 (the half-filled block) and beyond the variants
+            f4 bo0 = *reinterpret_cast<const f4*>(dout + v * 16 + 8 * (kk & 1)), bo1 = *reinterpret_cast<const f4*>(dout + v * 16 + 8 * (kk & 1) + 4);
+            if (r >= V || kk >= 2) bo0 = bo1 = c3_zero();
+            bf8 bh, bm;
+            c3w_split8(bo0, bo1, bh, bm);
 #pragma unroll
             for (int p = 0; p < L2; ++p)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const f4 d = c3_mfma4(*reinterpret_cast<const f4*>(W.wltf + ((p * 2 + t) * 64 + lane) * 4), bo, c3_zero());
-                    if (r < V) *reinterpret_cast<f4*>(x + (v * ST2 + p) * 32 + 16 * t + 4 * g) = d;  // rows = channels 16 t + 4 j + g
+                    const c3_u4* a = W.wltp + (p * 2 + t) * 2 * 32 + (lane & 31);
+                    const bf8 ah = __builtin_bit_cast(bf8, a[0]), am = __builtin_bit_cast(bf8, a[32]);
+                    f4 d = mfma_bf16(am, bh, c3_zero());
+                    d = mfma_bf16(ah, bm, d);
+                    d = mfma_bf16(ah, bh, d);
+                    if (r < V) *reinterpret_cast<f4*>(x + (v * ST2 + p) * C3X_F + 16 * t + 4 * g) = d;  // rows = channels 16 t + 4 j + g
                 }
         }
         c3_wave_sync();
         C3_EV();  // 1 done
-        // ---- 2. through the second activation: dY2 = d(a2) * act2'(a2), zero on padding columns; back to LDS for the
-        //         transposed reads; linear weight gradient ------------------------------------------------------------------
+        // ---- 2. through the second activation: dY2 = d(a2) * act2'(a2), zero on padding columns (kept in registers until a2 and
+        //         the fp32 d(a2) are dead); linear weight gradient ---------------------------------------------------------
+        f4 dy[N2T][2];
+#pragma unroll
         for (int T = 0; T < N2T; ++T) {
-            const int col = 16 * T + r;
-            int v = col / ST2;
-            const int p = col - v * ST2;
-            const bool valid = v < V && p < L2;
-            v = min(v, V - 1);
+            const int col = 16 * T + r, p = col % ST2;  // (N2T whole tiles: every column is a (variant, position) of the batch)
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                float* px = x + (v * ST2 + p) * 32 + 16 * t + 4 * g;
-                const f4 y = *reinterpret_cast<const f4*>(a2 + (v * ST2 + p) * 32 + 16 * t + 4 * g);
-                f4 d = *reinterpret_cast<const f4*>(px) * c3_act_grad4(c.act2, y);
-                if (!valid) d = c3_zero();
-                if (v < V && col < V * ST2) *reinterpret_cast<f4*>(px) = d;
+                const f4 y = *reinterpret_cast<const f4*>(a2 + col * 32 + 16 * t + 4 * g);
+                f4 d = *reinterpret_cast<const f4*>(x + col * C3X_F + 16 * t + 4 * g) * c3_act_grad4(c.act2, y);
+                if (p >= L2) d = c3_zero();
+                dy[T][t] = d;
                 gb2[t] = gb2[t] + d;
             }
         }
@@ -824,16 +870,24 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
                     for (int t = 0; t < 2; ++t) gwl[p][t] = mfma16(a, a2[(v * ST2 + p) * 32 + 16 * t + m], gwl[p][t]);  // B col m = element m of the block
             }
         }
-        c3_wave_sync();  // a2 is dead: the dY2 image takes its place, [position][v >> 2][element][v & 3]
+        // a2 is dead: the dY2 image takes its place, [position][v >> 2][element][v & 3] (phase 3's operand); the fp32 d(a2) is dead: dY2's
+        // bf16 pieces take its place, [column][piece][32 elements] (phase 4's operand)
+        c3_wave_sync();
 #pragma unroll
         for (int T = 0; T < N2T; ++T) {
             const int col = 16 * T + r, v = col / ST2, p = col - v * ST2;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const f4 d = *reinterpret_cast<const f4*>(x + col * 32 + 16 * t + 4 * g);  // (this lane's own stores of the loop above)
+                const f4 d = dy[T][t];
                 float* dst = dyt + p * C3T_POS + (v >> 2) * 128 + (16 * t + 4 * g) * 4 + (v & 3);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) dst[4 * j] = d[j];
+                unsigned h0, m0, h1, m1, unused = 0u;
+                split_pair<2>(d[0], d[1], h0, m0, unused);
+                split_pair<2>(d[2], d[3], h1, m1, unused);
+                unsigned char* px = xp + col * C3X_COL + (16 * t + 4 * g) * 2;
+                *reinterpret_cast<c3_u2*>(px) = c3_u2{h0, h1};
+                *reinterpret_cast<c3_u2*>(px + 64) = c3_u2{m0, m1};
             }
         }
         c3_wave_sync();
@@ -891,16 +945,25 @@ __global__ __launch_bounds__(64 * NW, 1) void pmt_cnn3_backward_kernel(
 #pragma unroll
             for (int tap = 0; tap < K2; ++tap) {
                 const int p = q - tap;
-                const bool ok = valid && p >= 0 && p < L2;
-                const float* src = x + (v * ST2 + (ok ? p : 0)) * 32 + 4 * g;
+                const bool ok = p >= 0 && p < L2;  // (a column beyond the variants reads a real one's: finite, and never stored)
+                constexpr int ZERO_P = L2 < ST2 ? L2 : 0;  // the padding position of every column holds zeros
+                const unsigned char* src = xp + (v * ST2 + (ok ? p : ZERO_P)) * C3X_COL + 16 * kk;  // k = record element 8 kk + i
+                c3_u4 bhw = *reinterpret_cast<const c3_u4*>(src), bmw = *reinterpret_cast<const c3_u4*>(src + 64);
+                if (L2 >= ST2 && !ok) bhw = bmw = c3_u4{0u, 0u, 0u, 0u};
+                const bf8 bh = __builtin_bit_cast(bf8, bhw), bm = __builtin_bit_cast(bf8, bmw);
+                bf8 ah[2], am[2];
 #pragma unroll
-                for (int kt = 0; kt < 2; ++kt) {
-                    f4 b = *reinterpret_cast<const f4*>(src + 16 * kt);
-                    if (!ok) b = c3_zero();
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-                        acc[mt] = c3_mfma4(*reinterpret_cast<const f4*>(W.w2tf + (((tap * 2 + mt) * 2 + kt) * 64 + lane) * 4), b, acc[mt]);
+                for (int mt = 0; mt < 2; ++mt) {
+                    const c3_u4* a = W.w2tp + (tap * 2 + mt) * 2 * 64 + lane;
+                    ah[mt] = __builtin_bit_cast(bf8, a[0]);
+                    am[mt] = __builtin_bit_cast(bf8, a[64]);
                 }
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) acc[mt] = mfma_bf16(am[mt], bh, acc[mt]);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) acc[mt] = mfma_bf16(ah[mt], bm, acc[mt]);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) acc[mt] = mfma_bf16(ah[mt], bh, acc[mt]);
             }
             if (valid) {
 #pragma unroll
