@@ -377,7 +377,12 @@ typedef struct PmtIntColumn {
 } PmtIntColumn;
 
 /* The (source, label, variant type, ref-count bin, alt-count bin) cell of a variant (reference data/batch.py:228-230,
- * data/count_binning.py:9-26): what the balancer's and the downsampler's tables are indexed by. */
+ * data/count_binning.py:9-26): what the balancer's and the downsampler's tables are indexed by.
+ * The caller's contract (the columns live on the device, no entry point can look at them): label in 0 .. 2, variant type in
+ * 0 .. num_variant_types - 1, ref count >= 0, alt count >= 1, source >= 0.  A value outside lands in another cell's arithmetic -- where the
+ * reference raises -- and is not diagnosed.  (An alt count of 0 would also differ from the reference: C division truncates (0 - 1) / skip
+ * to bin 0, the reference floors it to -1.)  A source >= num_sources, with the rest in range, is beyond every table and is passed over:
+ * see the entry points. */
 typedef struct PmtBinning {
     int32_t num_sources, num_variant_types, num_ref_bins, num_alt_bins, count_bin_skip, max_ref_count, max_alt_count, reserved;
 } PmtBinning;
@@ -874,7 +879,9 @@ int pmt_preprocess_normalize(const PmtPreprocessArgs* args, void* stream);
  * training/model_training.py:204-228 runs it three times per parent batch after every validation epoch): the weights of the LABELED
  * variants over (source, label, variant type, ref-count bin, alt-count bin, LOGIT bin) and, per label, the weight called artifact / not
  * and the weighted logit sum -- one launch for ~30 tensor ops.  `flat`: [2 epoch types][nhist] histograms, then [2][3 labels][3] statistics
- * (training/loss_recorder.py: EvaluationCounts.flat). */
+ * (training/loss_recorder.py: EvaluationCounts.flat).  The logit bin is floor((clamp(logit, min_logit, max_logit) - min_logit) /
+ * logit_bin_skip) exactly, taken as floor(clamp(logit)) and integer arithmetic (in float32 the subtraction rounds a logit just below a
+ * bin boundary onto it).  nhist must be the product of the dimensions: PMT_E_INVALID otherwise. */
 typedef struct PmtEvalArgs {
     int32_t num_variants, epoch_index;              /* 0: training data, 1: validation data */
     int32_t num_logit_bins, min_logit, max_logit, logit_bin_skip;   /* reference data/count_binning.py:14-26 */
@@ -896,7 +903,11 @@ int pmt_record_evaluation(const PmtEvalArgs* args, float* flat, void* stream);
  *             workgroup 0 stores them), then weights_b = labeled ? weights[cell] : p * unlabeled_weights[cell as artifact] +
  *             (1 - p) * unlabeled_weights[cell as variant], and source_weights_b = weights_b * source_weights[source]
  *             (BatchOutput.weights / .source_weights of reference artifact_model.py:285-288).
- * tables_in and tables_out must be different buffers when recompute != 0 (the caller swaps them). */
+ * tables_in and tables_out must be different buffers when recompute != 0 (the caller swaps them): PMT_E_INVALID otherwise.
+ * A variant whose source is >= num_sources adds to no table and gets weights_b = source_weights_b = 1.  A source without a variant
+ * so far has source weight inf after a recomputation (total / 0, as in the reference).  num_variants == 0: PMT_OK, nothing launched and
+ * nothing written, whatever `recompute` says.  num_sources beyond 16: PMT_E_INVALID; tables beyond 2048 floats (seven sources of the
+ * production bins): PMT_E_UNSUPPORTED. */
 typedef struct PmtBalanceArgs {
     int32_t num_variants, recompute;
     float attenuation;                  /* ATTENUATION_PER_DATUM ^ (variants since the last recomputation) */

@@ -168,7 +168,9 @@ __global__ __launch_bounds__(BAL_THREADS) void pmt_record_evaluation_kernel(PmtE
         if (label == BAL_LABEL_ARTIFACT || label == BAL_LABEL_VARIANT) {  // (unlabeled data are not tallied: reference evaluation_metrics.py:58-66)
             const int cell = cell_of(a.bins, col_at(a.sources, b), label, col_at(a.variant_types, b), col_at(a.ref_counts, b), col_at(a.alt_counts, b));
             const float clamped = fminf(fmaxf(logit, (float)a.min_logit), (float)a.max_logit);
-            const int lbin = (int)floorf((clamped - (float)a.min_logit) / (float)a.logit_bin_skip);
+            // floor first, integers afterwards: exact.  `clamped - min_logit` in float32 rounds a logit just below a bin boundary onto
+            // the boundary (-3.0000002 + 10 = 7.0), one bin too high.  (clamped >= min_logit: the integer division is the floor.)
+            const int lbin = ((int)floorf(clamped) - a.min_logit) / a.logit_bin_skip;
             const long long idx = (long long)cell * a.num_logit_bins + lbin;
             if (cell >= 0 && idx < a.nhist && lbin >= 0 && lbin < a.num_logit_bins) {
                 if (in_lds) atomicAdd(&hist[idx], w); else atomicAdd(&ghist[idx], w);

@@ -108,6 +108,14 @@ def logit_bin_indices(logits: torch.Tensor) -> torch.Tensor:
     return torch.div(torch.clamp(logits, min=MIN_LOGIT, max=MAX_LOGIT) - MIN_LOGIT, LOGIT_BIN_SKIP, rounding_mode="floor").long()
 
 
+def evaluation_logit_bins(logits: torch.Tensor) -> torch.Tensor:
+    """The logit bin of the evaluation tallies: floor((clamp(x) - MIN_LOGIT) / LOGIT_BIN_SKIP) EXACTLY.  In float32 the subtraction of
+    `logit_bin_indices` rounds a logit just below a bin boundary onto it (-3.0000002 + 10 is 7.0) and the logit lands one bin too high;
+    floor(clamp(x)) is exact in any float type and the rest is integer arithmetic (pmt_record_evaluation does the same)."""
+    whole = torch.floor(torch.clamp(logits, min=MIN_LOGIT, max=MAX_LOGIT)).long()
+    return torch.div(whole - MIN_LOGIT, LOGIT_BIN_SKIP, rounding_mode="floor")
+
+
 class EvaluationCounts:
     """What an evaluation pass leaves behind, on the device, read once at the end.
 
@@ -171,7 +179,7 @@ class EvaluationCounts:
         st.index_add_(0, labels * 3 + called, weights)
         st.index_add_(0, labels * 3 + 2, weights * logits)
         # reference evaluation_metrics.py:58-66: unlabeled data are not tallied (weight x is_labeled)
-        idx = flattened_slvra_index(batch) * NUM_LOGIT_BINS + logit_bin_indices(logits)
+        idx = flattened_slvra_index(batch) * NUM_LOGIT_BINS + evaluation_logit_bins(logits)
         self.flat[: 2 * self._nhist].view(2, -1)[epoch_index].index_add_(0, idx, weights * (labels != int(Label.UNLABELED)).float())
         self.batches += 1
 
