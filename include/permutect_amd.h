@@ -331,7 +331,8 @@ int pmt_build_id(char* out, int32_t capacity);
 /* sizeof() of the ABI structs as compiled into the library, for binding self-checks:
  * 0 PmtModel, 1 PmtBatch, 2 PmtOutputs, 3 PmtOutputGrads, 4 PmtAdamW, 5 PmtLinear, 6 PmtOp, 7 PmtMlp, 8 PmtBlock, 9 PmtHead,
  * 10 PmtPhiProgram, 11 PmtLossArgs, 12 PmtDownsample, 13 PmtRecordArgs, 14 PmtBalanceArgs, 15 PmtEvalArgs, 16 PmtPosteriorRows,
- * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs, 21 PmtPosteriorEvalArgs, 22 PmtAnnotateArgs */
+ * 17 PmtPosteriorParams, 18 PmtPruneArgs, 19 PmtPruneStats, 20 PmtWorstArgs, 21 PmtPosteriorEvalArgs, 22 PmtAnnotateArgs,
+ * 23 PmtPreprocessArgs, 24 PmtSiteKeysArgs, 25 PmtVcfArgs */
 int pmt_struct_bytes(int which);
 
 /* Validates a descriptor against the kernels' limits. */
@@ -812,6 +813,91 @@ typedef struct PmtAnnotateArgs {
  * (no output, counter or row pointer is looked at).  A NULL struct, output, counters or int_rows, num_candidates < 0 or beyond 2^31 - 1, a table size < 0 or beyond 2^31 - 1, a NULL array of a
  * non-empty table, an element width other than 2 / 4 / 8, first_column < 0 or a row shorter than first_column + 7, or a threads_hint not listed: PMT_E_INVALID, nothing launched. */
 int pmt_annotate_sites(const PmtAnnotateArgs* args, void* stream);
+
+/* The filtered VCF of filter_variants (reference tools/filter_variants.py:369-617 `apply_filtering_to_vcf`): the reference keeps a dict
+ * of PosteriorResults keyed by the string `contig:pos:alt` and, per cyvcf2 record, looks it up, formats 21 numbers with "{:.3f}" and
+ * joins a set of filter names.  Here the VCF's data lines lie on the device as bytes beside a table of numbers per line (what
+ * permutect_amd/data/vcf_text.py reads), and four entries do the rest; the caller sorts between the first and the second and turns the
+ * lengths into starts between the third and the fourth.  INTEGER ARITHMETIC ONLY: every output byte is the same for any grid, any
+ * slab and from run to run.
+ *   THE RULE.  A record's key is (CHROM, POS as written, truncate(trim(REF, ALT[0]).alt)) as a 64-bit locus and a 32-bit allele key,
+ *   the candidates' keys being those of pmt_annotate_sites.  Records with one key match each on their own; of candidates with one key
+ *   the LAST in dataset order wins (the reference's dict overwrites).  A record without PMT_VCF_HAS_KEY never matches.
+ *   FILTER is a set: those of `contamination`, `slippage` that the record's own FILTER column holds; for a record that matches row r
+ *   with filtered[r] != 0, the lower-case name of the error call: the call with the largest float32 posterior probability among the
+ *   four that are not `passing_call`, the lowest index among equal maxima; for a record that matches nothing and carries
+ *   PMT_VCF_ZERO_ALT_DEPTH, `seq_error`.  It is written in ONE order -- contamination, slippage, then somatic, artifact, seq_error,
+ *   germline, normal_artifact -- joined by `;`, and as PASS when empty.
+ *   INFO of a matched record gets `;POST=p0,..,p4;PRIOR=..;SPECLL=..;ARTLOD=x;NORMLL=..` appended (values [r, 0 .. 20] in this order);
+ *   an INFO column that is `.` is replaced by that text without its leading `;`.  Every other byte of the line is copied.
+ *   A NUMBER is Python's "{:.3f}".format(float(x)) of the float32 x = +-m * 2^e: q = round_half_even(m * 1000 * 2^e) -- a shift for
+ *   e >= 0, a shift and one compare of the remainder with the half for -64 < e < 0, 0 below -- printed with four digits at least and a
+ *   point before the last three, `-` whenever the sign bit is set; `nan`, `inf`, `-inf`.  A finite |x| >= 2^53 is NOT formatted: it
+ *   takes no bytes and is counted; the caller refuses to write such a file.
+ * counters (PMT_VCF_COUNTERS uint64, ADDED to by pmt_vcf_plan: the caller zeroes them): matched, unmatched, zero alt depth, passed
+ * (written as PASS), records carrying each of the five call names, records with a trusted filter kept, matched records whose own
+ * Variation differs from their candidate's, unformattable values -- integer atomics, one per non-zero counter per workgroup. */
+#define PMT_VCF_CONTAMINATION 1
+#define PMT_VCF_SLIPPAGE 2
+#define PMT_VCF_HAS_KEY 4
+#define PMT_VCF_INFO_DOT 8
+#define PMT_VCF_VERBATIM 16        /* a line that is no record (blank, or `#` behind the header): copied as it stands */
+#define PMT_VCF_ZERO_ALT_DEPTH 32
+#define PMT_VCF_COUNTERS 12
+#define PMT_VCF_VALUES 21
+typedef struct PmtSiteKeysArgs {
+    int64_t num_candidates;                    /* up to 2^31 - 1 */
+    const void* int_rows;                      /* as in PmtAnnotateArgs */
+    int64_t int_row_stride;
+    int32_t int_elem_bytes, first_column;
+    int32_t threads_hint, reserved;            /* workgroup size 64 / 128 / 256 / 512 / 1024, 0 = 256 */
+    uint64_t* locus;                           /* [num_candidates] out */
+    uint32_t* allele_key;                      /* [num_candidates] out */
+} PmtSiteKeysArgs;
+typedef struct PmtVcfArgs {
+    int64_t num_records;                       /* lines behind the header, up to 2^31 - 1 */
+    int64_t first_record, count;               /* pmt_vcf_write: the slab's records [first_record, first_record + count) */
+    int32_t threads_hint, passing_call;        /* workgroup size as above; 0 .. 4 */
+    const int64_t* line_start;                 /* [num_records + 1] byte offset of every line in the text; the last: its end */
+    const int32_t* filter_begin;               /* [num_records] offsets inside the line: the FILTER column's begin, */
+    const int32_t* filter_end;                 /*   its end (the tab in front of INFO) */
+    const int32_t* info_end;                   /*   and the INFO column's end */
+    const uint64_t* rec_locus;                 /* [num_records] */
+    const uint32_t* rec_key;
+    const uint8_t* rec_flags;                  /* PMT_VCF_* */
+    const uint8_t* rec_variation;              /* the record's own Variation: len(ALT[0]) - len(REF) */
+    int64_t num_candidates;                    /* up to 2^31 - 1 */
+    const uint64_t* cand_locus;                /* [num_candidates] ascending by (locus, key, row) */
+    const uint32_t* cand_key;
+    const int64_t* cand_row;                   /* the dataset row of every sorted entry */
+    const float* values;                       /* [num_candidates, 21] by dataset row */
+    const uint8_t* filtered;                   /* [num_candidates] */
+    const uint8_t* variant_types;              /* [num_candidates] */
+    int32_t* matched;                          /* [num_records] out of match, in of plan and write: the row or -1 */
+    uint8_t* mask;                             /* [num_records] out of plan, in of write: bit 0 contamination, 1 slippage, 2 + c call c */
+    int8_t* error_call;                        /* [num_records] out of plan: the error call or -1 */
+    int64_t* out_length;                       /* [num_records] out of plan: the bytes of the output line */
+    uint64_t* counters;                        /* [PMT_VCF_COUNTERS] added to by plan */
+    const int64_t* out_start;                  /* [num_records + 1] in of write: the exclusive sums of out_length */
+    const uint8_t* text;                       /* in of write: text byte t stands at text[t - text_base], text_base <= t < text_base + text_bytes */
+    int64_t text_base, text_bytes;
+    uint8_t* out;                              /* out of write: output byte o goes to out[o - out_base], likewise */
+    int64_t out_base, out_bytes;
+} PmtVcfArgs;
+/* Each entry: ordinary launches on `stream`; no allocation, no synchronisation, no host read-back.  A count of 0 (candidates for
+ * pmt_site_keys, records for match and plan, `count` for write): PMT_OK, nothing launched.  A NULL struct or needed pointer, a size < 0
+ * or beyond 2^31 - 1, a threads_hint not listed, passing_call outside 0 .. 4, an element width other than 2 / 4 / 8, a row shorter than
+ * first_column + 7, a slab outside the records, or negative text / out sizes: PMT_E_INVALID, nothing launched.
+ *   pmt_site_keys: a lane per candidate, identity columns -> locus and allele key.
+ *   pmt_vcf_match: a lane per record; ceil(log2(num_candidates + 1)) probes of the sorted keys, every lane the same number.
+ *   pmt_vcf_plan: a lane per record: mask, error_call, out_length, counters.  Needs `matched`.
+ *   pmt_vcf_write: a wavefront per record of the slab: lanes 0 .. 20 format a value each, a prefix sum places them, then all lanes copy
+ *   the line's pieces, consecutive lanes on consecutive bytes.  No byte outside text[0, text_bytes) is read, none outside
+ *   out[0, out_bytes) written. */
+int pmt_site_keys(const PmtSiteKeysArgs* args, void* stream);
+int pmt_vcf_match(const PmtVcfArgs* args, void* stream);
+int pmt_vcf_plan(const PmtVcfArgs* args, void* stream);
+int pmt_vcf_write(const PmtVcfArgs* args, void* stream);
 
 /* The normalisation of preprocess_dataset (reference data/plain_text_data.py:205-479: `normalized_data_generator`,
  * `make_read_quantile_transform`, `normalize_raw_data_list`; sklearn's QuantileTransformer and numpy's nanpercentile / interp behind

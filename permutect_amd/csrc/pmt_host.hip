@@ -46,6 +46,8 @@ extern "C" int pmt_struct_bytes(int which) {
         case 21: return (int)sizeof(PmtPosteriorEvalArgs);
         case 22: return (int)sizeof(PmtAnnotateArgs);
         case 23: return (int)sizeof(PmtPreprocessArgs);
+        case 24: return (int)sizeof(PmtSiteKeysArgs);
+        case 25: return (int)sizeof(PmtVcfArgs);
         default: return PMT_E_INVALID;
     }
 }

@@ -14,7 +14,6 @@ Plain Python and numpy: neither cyvcf2 nor intervaltree is used."""
 from __future__ import annotations
 
 import ctypes as C
-import gzip
 import os
 from dataclasses import dataclass, field
 from typing import Dict, Optional
@@ -169,12 +168,6 @@ def decode_identity(identity: np.ndarray):
 
 
 # ---- the host readers --------------------------------------------------------------------------------------------------------------------
-def _open_text(path):
-    with open(path, "rb") as probe:
-        magic = probe.read(2)
-    return gzip.open(path, "rt") if magic == b"\x1f\x8b" else open(path, "r")
-
-
 def _popaf(info: str, line_number: int, path) -> float:
     for entry in info.split(";"):
         if entry.startswith("POPAF="):
@@ -195,37 +188,12 @@ def read_vcf_sites(path, contig_index_by_name: Dict[str, int]) -> SiteTable:
 
     POPAF goes through float32 first: htslib hands cyvcf2 a 32-bit Float.  That step rests on the two libraries' documentation; it
     could not be checked against a cyvcf2 installation."""
-    loci, alts, popafs, excluded_flags = [], [], [], []
-    skipped = {"unknown_contig": 0, "no_alt": 0, "not_acgt": 0}
-    num_records = 0
-    with _open_text(path) as file:
-        for line_number, line in enumerate(file, start=1):
-            if line.startswith("#") or not line.strip():
-                continue
-            num_records += 1
-            tokens = line.rstrip("\r\n").split("\t", 8)
-            if len(tokens) < 8:
-                raise ValueError(f"{path}, line {line_number}: a VCF data line has eight tab-separated columns at least")
-            popaf = _popaf(tokens[7], line_number, path)
-            contig = contig_index_by_name.get(tokens[0])
-            if contig is None:
-                skipped["unknown_contig"] += 1
-                continue
-            alt = tokens[4].split(",")[0]
-            if alt == "." or alt == "":
-                skipped["no_alt"] += 1
-                continue
-            key = vcf_allele_key(tokens[3], alt)
-            if key is None:
-                skipped["not_acgt"] += 1
-                continue
-            position = int(tokens[1])
-            if not 0 <= position <= 0xFFFFFFFF:
-                raise ValueError(f"{path}, line {line_number}: POS {position} does not fit 32 bits")
-            loci.append(locus_key(contig, position))
-            alts.append(key)
-            popafs.append(popaf)
-            excluded_flags.append(not TRUSTED_M2_FILTERS.isdisjoint(tokens[6].split(";")))
+    from permutect_amd.data.vcf_text import read_vcf  # (the one pass over the file, shared with the filtered VCF's record table)
+    return read_vcf(path, contig_index_by_name).sites
+
+
+def site_table(path, loci, alts, popafs, excluded_flags, contig_index_by_name: Dict[str, int], num_records: int, skipped: Dict[str, int]) -> SiteTable:
+    """the keyed records of a VCF in file order -> the SiteTable (`read_vcf_sites`)"""
     locus, alt = np.array(loci, np.uint64), np.array(alts, np.uint32)
     try:
         frequencies = [10.0 ** -float(p) for p in np.array(popafs, np.float32)]

@@ -253,6 +253,22 @@ class PmtPreprocessArgs(C.Structure):
                 ("out_reads", vp), ("out_floats", vp), ("fault", vp)]
 
 
+class PmtSiteKeysArgs(C.Structure):
+    _fields_ = [("num_candidates", i64), ("int_rows", vp), ("int_row_stride", i64), ("int_elem_bytes", i32), ("first_column", i32),
+                ("threads_hint", i32), ("reserved", i32), ("locus", vp), ("allele_key", vp)]
+
+
+class PmtVcfArgs(C.Structure):
+    _fields_ = [("num_records", i64), ("first_record", i64), ("count", i64), ("threads_hint", i32), ("passing_call", i32),
+                ("line_start", vp), ("filter_begin", vp), ("filter_end", vp), ("info_end", vp), ("rec_locus", vp), ("rec_key", vp),
+                ("rec_flags", vp), ("rec_variation", vp), ("num_candidates", i64), ("cand_locus", vp), ("cand_key", vp), ("cand_row", vp),
+                ("values", vp), ("filtered", vp), ("variant_types", vp), ("matched", vp), ("mask", vp), ("error_call", vp),
+                ("out_length", vp), ("counters", vp), ("out_start", vp), ("text", vp), ("text_base", i64), ("text_bytes", i64),
+                ("out", vp), ("out_base", i64), ("out_bytes", i64)]
+
+
+VCF_COUNTERS, VCF_VALUES = 12, 21  # PMT_VCF_COUNTERS, PMT_VCF_VALUES
+
 # PMT_PREPROCESS_QUANTILES, _KEYS, _PPF, _MAX_ALT, _READ_BYTES
 PREPROCESS_QUANTILES, PREPROCESS_KEYS, PREPROCESS_PPF, PREPROCESS_MAX_ALT, PREPROCESS_READ_BYTES = 100, 65536, 15361, 15, 12
 
@@ -266,7 +282,7 @@ EXPORTS = ["pmt_abi_version", "pmt_build_id", "pmt_shape_info", "pmt_shape_id", 
            "pmt_cnn_bn_forward", "pmt_cnn_bn_backward", "pmt_cnn_bn_workspace_floats",
            "pmt_cnn_bn_forward_moments", "pmt_cnn_bn_backward_moments", "pmt_cnn_bn_merge", "pmt_cnn_bn_forward_full", "pmt_cnn_bn_backward_full",
            "pmt_phi_forward", "pmt_phi_backward", "pmt_build_read_index", "pmt_losses_forward", "pmt_losses_backward",
-           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_annotate_sites", "pmt_preprocess_fit", "pmt_preprocess_normalize", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
+           "pmt_downsample_counts", "pmt_downsample_index", "pmt_downsample_fit", "pmt_spectra_fit", "pmt_posterior_forward", "pmt_posterior_step", "pmt_posterior_step_context", "pmt_posterior_evaluate", "pmt_context_priors_fit", "pmt_posterior_update", "pmt_record_losses", "pmt_prune_scratch_bytes", "pmt_prune_thresholds", "pmt_prune_select", "pmt_worst_table_bytes", "pmt_worst_scratch_bytes", "pmt_worst_record", "pmt_worst_merge", "pmt_annotate_sites", "pmt_preprocess_fit", "pmt_preprocess_normalize", "pmt_site_keys", "pmt_vcf_match", "pmt_vcf_plan", "pmt_vcf_write", "pmt_record_evaluation", "pmt_balance_step", "pmt_posterior_rows",
            "pmt_plan_groups_split", "pmt_layered_scratch_floats", "pmt_forward_layered",
            "pmt_layered_backward_scratch_floats", "pmt_backward_layered", "pmt_host_copy", "pmt_pack_order", "pmt_pack_order_batches", "pmt_prepare_chunk", "pmt_host_copy_rows", "pmt_compose_batch", "pmt_compose_batch_planned"]
 
@@ -348,6 +364,10 @@ def load(path: str = None) -> C.CDLL:
     lib.pmt_annotate_sites.argtypes = [P(PmtAnnotateArgs), vp]
     lib.pmt_preprocess_fit.argtypes = [P(PmtPreprocessArgs), vp]
     lib.pmt_preprocess_normalize.argtypes = [P(PmtPreprocessArgs), vp]
+    lib.pmt_site_keys.argtypes = [P(PmtSiteKeysArgs), vp]
+    lib.pmt_vcf_match.argtypes = [P(PmtVcfArgs), vp]
+    lib.pmt_vcf_plan.argtypes = [P(PmtVcfArgs), vp]
+    lib.pmt_vcf_write.argtypes = [P(PmtVcfArgs), vp]
     lib.pmt_plan_groups_split.argtypes = [vp, vp, i32, vp, vp, i32, P(i32)]
     lib.pmt_layered_scratch_floats.argtypes = [P(PmtModel), i64, i32]
     lib.pmt_layered_scratch_floats.restype = C.c_size_t
@@ -393,7 +413,7 @@ def load(path: str = None) -> C.CDLL:
     for which, st in enumerate([PmtModel, PmtBatch, PmtOutputs, PmtOutputGrads, PmtAdamW, PmtLinear, PmtOp, PmtMlp,
                                 PmtBlock, PmtHead, PmtPhiProgram, PmtLossArgs, PmtDownsample, PmtRecordArgs, PmtBalanceArgs, PmtEvalArgs,
                                 PmtPosteriorRows, PmtPosteriorParams, PmtPruneArgs, PmtPruneStats, PmtWorstArgs, PmtPosteriorEvalArgs,
-                                PmtAnnotateArgs, PmtPreprocessArgs]):
+                                PmtAnnotateArgs, PmtPreprocessArgs, PmtSiteKeysArgs, PmtVcfArgs]):
         if lib.pmt_struct_bytes(which) != C.sizeof(st):
             raise PmtError(f"ctypes layout of {st.__name__} ({C.sizeof(st)} B) does not match the library "
                            f"({lib.pmt_struct_bytes(which)} B)")

@@ -1,8 +1,8 @@
 """The artifact-model stage of `filter_variants` on the MI355X engine (reference tools/filter_variants.py:292-320, :350-357:
 `generate_posterior_data` + `MemoryMappedData.from_generator`): every candidate of a dataset tar goes through the model's forward and
 comes out as a read-less Datum row whose info array is its embedding and whose CACHED_ARTIFACT_LOGIT is its logit -- the input of
-the posterior model.  What stands in front of this stage in the reference (plain-text parsing) and the filtered VCF behind it are out
-of scope: the tool reads a dataset tar in the reference's format and writes the posterior data as a tar in the same format.
+the posterior model.  The tool reads a dataset tar in the reference's format (or, with --test_dataset, Mutect2's plain text) and writes
+the posterior data as a tar in the same format; the stages behind it are switched on by their flags, below.
 
     python -m permutect_amd.tools.filter_variants --test_dataset_tar candidates.tar --artifact_model model.pt --output posterior.tar
 
@@ -33,6 +33,15 @@ tallies the error logit by label, the cached artifact logit by most-confident ca
 integer tables; the .npz holds the tables, the sensitivity / precision curve of every variant type over all counts
 (metrics/accuracy_curves.py), the thresholds as logits, sensitivity and precision at those thresholds, and the row indices and bad calls
 of the mistakes.  The filter decisions are the `filtered_b` of --calls_output, passed on.  The reference's plots are not drawn.
+
+With `--output_vcf PATH` (needs --input, --contigs_table and --genomic_span; reference tools/filter_variants.py:369-617
+`apply_filtering_to_vcf`) rank 0 then writes the filtered VCF (tools/filtered_vcf.py; csrc/pmt_vcf.hip): every record of --input finds
+its candidate on the device, gets its FILTER text (the trusted Mutect2 filters it had, the error call's name when its candidate is
+filtered, `seq_error` when it has no candidate and no alt depth) and, with a candidate, POST, PRIOR, SPECLL, ARTLOD and NORMLL formatted
+as Python's `{:.3f}`; every other byte is the input's.  The VCF is read once per run: the site annotation and the writer share the pass
+(data/vcf_text.py).  The decisions are again the `filtered_b` of --calls_output.  Plain text, or gzip when PATH ends in `.gz`.
+
+    ... --input in.vcf --contigs_table contigs.table --genomic_span 3e9 --calls_output calls.npz --output_vcf filtered.vcf
 
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N -m permutect_amd.tools.filter_variants ...`: WORLD_SIZE > 1) the
 candidates are cut into N contiguous shards, one process per GPU, no collective on the data path; rank 0 concatenates the shards'
@@ -68,8 +77,10 @@ def main_without_parsing(args, log=print):
     dist, rank, world, device = init_from_env()  # this rank's card and the process group, before anything else touches the GPU
     model, _, _ = load_model(getattr(args, ARTIFACT_MODEL_NAME), device=device)
     data = load_candidates(args, device)
+    vcf = None
     if getattr(args, constants.INPUT_NAME, None) is not None:
-        data = annotate_candidates(args, data, device, log if rank == 0 else (lambda *a, **k: None))
+        vcf = read_input_vcf(args)
+        data = annotate_candidates(args, data, device, log if rank == 0 else (lambda *a, **k: None), vcf=vcf)
     dataset = ReadsDataset(data)
     t0 = time.perf_counter()
     posterior = make_posterior_mmap(dataset, model, getattr(args, constants.BATCH_SIZE_NAME), device=device,
@@ -80,7 +91,7 @@ def main_without_parsing(args, log=print):
             "disk to posterior rows)")
         posterior.save_to_tarfile(getattr(args, constants.OUTPUT_NAME))
         if posterior_stage_requested(args):  # (sequential: under torchrun the other ranks wait at the barrier below)
-            run_posterior_stage(args, posterior, device, log)
+            run_posterior_stage(args, posterior, device, log, vcf=vcf)
     if dist is not None:
         dist.barrier()
     return posterior
@@ -97,16 +108,26 @@ def load_candidates(args, device) -> MemoryMappedData:
     return make_normalized_mmap_data([text], device=device)
 
 
-def annotate_candidates(args, data: MemoryMappedData, device, log=print) -> MemoryMappedData:
+def read_input_vcf(args):
+    """--input read ONCE (data/vcf_text.py): the site table of the annotation and, for --output_vcf, the header and the record table"""
+    from permutect_amd.data import site_annotation as S
+    from permutect_amd.data.vcf_text import read_vcf
+    contigs_path = getattr(args, CONTIGS_TABLE_NAME, None)
+    if contigs_path is None:
+        raise ValueError(f"--{constants.INPUT_NAME} names candidates by contig name: it needs --{CONTIGS_TABLE_NAME}")
+    return read_vcf(getattr(args, constants.INPUT_NAME), S.read_contig_indices(contigs_path))
+
+
+def annotate_candidates(args, data: MemoryMappedData, device, log=print, vcf=None) -> MemoryMappedData:
     """--input: the three annotated float columns from the VCF and the segment files, the candidates outside the VCF or with a trusted
-    Mutect2 filter dropped (data/site_annotation.py)"""
+    Mutect2 filter dropped (data/site_annotation.py).  `vcf`: the input VCF as `read_input_vcf` has read it (else it is read here)."""
     from permutect_amd.data import site_annotation as S
     contigs_path = getattr(args, CONTIGS_TABLE_NAME, None)
     if contigs_path is None:
         raise ValueError(f"--{constants.INPUT_NAME} names candidates by contig name: it needs --{CONTIGS_TABLE_NAME}")
     t0 = time.perf_counter()
     contigs = S.read_contig_indices(contigs_path)
-    sites = S.read_vcf_sites(getattr(args, constants.INPUT_NAME), contigs)
+    sites = vcf.sites if vcf is not None else S.read_vcf_sites(getattr(args, constants.INPUT_NAME), contigs)
     segments = S.read_segments(getattr(args, MAF_SEGMENTS_NAME, None), contigs)
     normal_segments = S.read_segments(getattr(args, NORMAL_MAF_SEGMENTS_NAME, None), contigs)
     t1 = time.perf_counter()
@@ -141,7 +162,7 @@ def posterior_outputs(model, rows, thresholds, losses, germline_mode: bool) -> d
     return {k: v.detach().cpu().numpy() for k, v in out.items()}
 
 
-def run_posterior_stage(args, posterior: MemoryMappedData, device, log=print):
+def run_posterior_stage(args, posterior: MemoryMappedData, device, log=print, vcf=None):
     import numpy as np
     from permutect_amd.architecture.posterior_model import PosteriorModel, PosteriorRows
     germline_mode, no_germline_mode = getattr(args, "germline_mode", False), getattr(args, "no_germline_mode", False)
@@ -167,7 +188,27 @@ def run_posterior_stage(args, posterior: MemoryMappedData, device, log=print):
             "(a deterministic estimator of the reference's model, not its ADVI fit)")
     if getattr(args, "evaluation_output", None):
         run_evaluation(args, posterior, rows, model, thresholds, out["filtered_b"], germline_mode, log)
+    if getattr(args, "output_vcf", None):
+        run_output_vcf(args, posterior, rows, out, germline_mode, device, vcf, log)
     return model, out
+
+
+def run_output_vcf(args, posterior: MemoryMappedData, rows, out, germline_mode: bool, device, vcf=None, log=print):
+    """--output_vcf: the input VCF with the filters and the five INFO fields of the calls just written (tools/filtered_vcf.py).  The
+    filter decisions are the `filtered_b` of --calls_output, passed on."""
+    import numpy as np
+    from permutect_amd.enums import Call
+    from permutect_amd.tools.filtered_vcf import write_filtered_vcf
+    t0 = time.perf_counter()
+    vcf = read_input_vcf(args) if vcf is None else vcf
+    t1 = time.perf_counter()
+    outputs = dict(out, artifact_logits_b=rows.artifact_logits.detach().float().cpu().numpy())
+    int_rows = np.asarray(posterior.int_mmap[: posterior.num_data])
+    counts = write_filtered_vcf(vcf.records, vcf.header, int_rows, outputs, Call.GERMLINE if germline_mode else Call.SOMATIC, device,
+                                getattr(args, "output_vcf"))
+    log(f"filtered VCF: {len(vcf.records)} lines, " + ", ".join(f"{name} {count}" for name, count in counts.items())
+        + (f"; read {t1 - t0:.3f} s," if t1 - t0 > 1e-4 else ";") + f" match, plan and write {time.perf_counter() - t1:.3f} s")
+    return counts
 
 
 def run_evaluation(args, posterior: MemoryMappedData, rows, model, thresholds, filtered_b, germline_mode: bool, log=print):
@@ -226,6 +267,9 @@ def parse_arguments(argv=None):
                              "estimator of the reference's model, not its ADVI fit)")
     parser.add_argument("--evaluation_output", type=str, default=None, required=False,
                         help="output .npz of the calls scored against the candidates' truth labels (with --genomic_span)")
+    parser.add_argument("--output_vcf", type=str, default=None, required=False,
+                        help="output path of the filtered VCF: --input with the filters and POST, PRIOR, SPECLL, ARTLOD, NORMLL of the calls "
+                             "(with --input and --genomic_span; gzip when it ends in .gz)")
     parser.add_argument("--recall_weight", type=float, default=1.0, required=False, help="weight of recall against precision in the F-beta score")
     args = parser.parse_args(argv)
     if getattr(args, constants.INPUT_NAME) is not None and getattr(args, CONTIGS_TABLE_NAME) is None:
@@ -237,6 +281,10 @@ def parse_arguments(argv=None):
         parser.error("--genomic_span runs the posterior stage, which needs --calls_output")
     if args.evaluation_output and not posterior_stage_requested(args):
         parser.error("--evaluation_output scores the posterior stage's calls, which needs --genomic_span")
+    if args.output_vcf and getattr(args, constants.INPUT_NAME) is None:
+        parser.error(f"--output_vcf rewrites the records of --{constants.INPUT_NAME}, which is missing")
+    if args.output_vcf and not posterior_stage_requested(args):
+        parser.error("--output_vcf writes the posterior stage's calls, which needs --genomic_span")
     return args
 
 
